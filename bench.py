@@ -131,6 +131,22 @@ def emit_result(res, compact=True):
     print(compact_line(res) if compact else full, flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each 2-D array as d/<name>.npy in float64.  The total stays within `limit`: an array over its share
+    keeps a fixed seeded sample of its columns (the same columns for the same shape, so two builds compare entry for entry)."""
+    os.makedirs(d, exist_ok=True)
+    share = limit // len(arrays)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            keep = share // (a.shape[0] * 8)
+            a = a[:, np.sort(np.random.default_rng(0).choice(a.shape[1], size=keep, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def synth_pairs(Ns, nz=6, m=3, seed=0):
     rng = np.random.default_rng(seed)
     alpha = rng.uniform(-1, 1, (Ns, nz)); u = rng.uniform(-1, 1, (Ns, m))
@@ -772,7 +788,11 @@ def main():
     ap.add_argument("--rand-systems", type=int, default=1024)
     ap.add_argument("--one-caller", action="store_true", help="(internal) the single-process multi-GPU block: kp_multi_* over --gpus devices")
     ap.add_argument("--no-one-caller", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (K, float64) as DIR/K.npy, for output-for-output comparison of builds")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.one_caller:
         one_caller_main(args)
         return
@@ -849,6 +869,8 @@ def main():
     # every K of the timed region is retrievable and they all solve the same system
     K_first, K_last = ctx.fit_result(0, W), ctx.fit_result(args.steps - 1, W)
     k_spread = float(np.abs(K_first - K_last).max())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"K": K_last})
     # ... and what bringing ALL of them to the host costs (a sweep that keeps every K): page-locked destination, direct DMA
     n_f = min(args.steps, 64)
     ctx.fit_results(0, n_f, W)

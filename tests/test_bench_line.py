@@ -131,3 +131,24 @@ def test_compact_line_of_the_committed_full_record():
         assert k in d, k
     assert abs(d["value"] / res["value"] - 1) < 1e-5 and d["roofline"]["bound"] == "mfma" and 0.5 < d["roofline"]["frac"] < 1.0
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] >= 1
+
+
+def test_dump_outputs_writes_float64_arrays_and_a_fixed_sample_of_large_ones(tmp_path):
+    import numpy as np
+    K = np.asfortranarray(np.random.default_rng(3).standard_normal((336, 336)))
+    bench.dump_outputs(str(tmp_path / "a"), {"K": K})
+    got = np.load(tmp_path / "a" / "K.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, K)
+    big = np.arange(64 * 100, dtype=np.float64).reshape(64, 100)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"K": big}, limit=64 * 8 * 10)
+    b, c = np.load(tmp_path / "b" / "K.npy"), np.load(tmp_path / "c" / "K.npy")
+    assert b.shape == (64, 10) and b.nbytes <= 64 * 8 * 10 and np.array_equal(b, c)
+    cols = (b[0] % 100).astype(int)
+    assert np.array_equal(b, big[:, cols]) and np.all(np.diff(cols) > 0)
+
+
+def test_bench_refuses_fewer_than_one_timed_step():
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and "--steps" in r.stderr

@@ -253,7 +253,8 @@ def test_stored_matlab_inputs_are_optimal_for_the_restated_qp(arm, golden, mt, k
 def test_stored_circle_runs_under_load_pin_lift_and_inputs_on_867_more_matlab_steps(arm, golden):
     """Golden vectors: simulations/circle_c0-0p7_r0p3_15sec/bilinear_..._16-43.mat res{1..3} - three more closed loops of the
     SAME N = 34 bilinear model (the plant carries loads W = -pi/3, 0, +pi/3; the controller does not know them), each with
-    Y, U, R, Z.  (a) The stored lifted states Z (300 x 34 x 3) are reproduced to 2e-14.  (b) Teacher-forced replay of the stored
+    Y, U, R, Z.  (a) The stored lifted states Z (300 x 34 x 3) are reproduced: the columns without the PCA to 2e-15, the PCA
+    columns to the rounding of the SVD, which depends on the BLAS kernel (1e-13).  (b) Teacher-forced replay of the stored
     inputs: the largest stored increment is 0.0789 = 0.01 * mean(u_factor) * u_factor(1), i.e. these runs used
     input_slopeConst = 1e-2 (everything else example_control.m, no input box: run 3 leaves it); the controller's reference
     window at step k is ref_sc(k : k+Np) (Ksim.m:198-202) and results.R(j) = ref(j-1) (:252 appends ref_sc(k) AFTER the step),
@@ -265,7 +266,11 @@ def test_stored_circle_runs_under_load_pin_lift_and_inputs_on_867_more_matlab_st
     med = []
     for i in range(3):
         Y, U, R, Z = (c[f"run{i}_{k}"] for k in "YURZ")
-        assert np.abs(ko.econ_full(dic, ko.scaledown(sc, "y", Y[:300])) - Z).max() < 2e-14
+        L = ko.econ_full(dic, ko.scaledown(sc, "y", Y[:300]))
+        assert np.abs(L[:, :6] - Z[:, :6]).max() < 2e-15 and np.array_equal(L[:, -1], Z[:, -1])     # [zeta ; ... ; 1]: no PCA in these
+        # pcs' * lift.full: the rounding of the float64 SVD behind pcs depends on the BLAS kernel the CPU selects (measured
+        # against Z, entries up to 3.9: 1.2e-14 with OpenBLAS's SkylakeX kernels, 2.2e-14 Sandybridge, 4.2e-14 Haswell / Zen)
+        assert np.abs(L - Z).max() < 1e-13
         assert abs(np.abs(np.diff(U, axis=0)).max() - 1e-2 * sc["u_factor"].mean() * sc["u_factor"][0]) < 1e-7     # quadprog interior point: 2e-9 inside the slope row
         ref = (R[1:] - sc["y_offset"][-2:]) / sc["y_factor"][-2:]                                   # scaledown_ref, Kmpc.m:135-142
         d = np.empty(289)
