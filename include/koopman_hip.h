@@ -335,6 +335,24 @@ int kp_mpc_step_zeta(kp_mpc* mpc, const kp_basis* basis, const double* zeta, con
                      const double* Yr, int iters, double* U_out, double* z_out, int* status);
 int kp_mpc_step_batch(kp_mpc* mpc, int nb, const double* z, const double* u_prev, const double* Yr,
                       double* U_out, int* status);
+/* kp_mpc_step_loaded: one step of a controller of a LOADED model (Ksysid loaded = true) with the load observer fused in
+ *   front, one launch: Kmpc.estimate_load_linear (Kmpc.m:1298-1356) / estimate_load_bilinear (:1360-1444) over the
+ *   window, then the loaded lift z = [psi; w_1 psi; ...; w_nw psi] of zeta (Ksysid.m:1606-1612, Kmpc.m:839-840) and the
+ *   step of kp_mpc_step (warm start, state bounds and iters alike).  Ksim.run_trial_mpc calls this every step of a
+ *   loaded closed loop (Ksim.m:169-194).
+ *   basis: the UNLOADED dictionary (N = basis N); the controller's width must be N (nw + 1).  1 <= nw <= 8.
+ *   zeta_win: (nobs + 1) x nzeta, row i = zeta_i of the window (row-major); u_win: nobs x m, row i = the input of
+ *   sample i in the regression (linear: upast(nd + i), bilinear: upast(i), as the reference indexes them).
+ *   0 <= nobs <= 64; nobs = 0 skips the estimate and lifts with what_prev as it is (the steps with
+ *   mod(k, load_obs_period) ~= 0, Ksim.m:187-189).  The estimate is the lsqlin of Kmpc.m:1354 / :1442: x = [1; w],
+ *   -1 <= w <= 1; flags KP_LOAD_RATE (1): also |w_i - what_prev_i| <= 0.01 (:1344-1347); KP_LOAD_PIN_LAST (2): the last
+ *   load pinned to zero (the debugging equality of :1350, which the reference applies to linear models with nw = 2).
+ *   what_out (nw) and *resnorm (||R x - d||^2) are written; when the estimate's QP fails they are NaN, U_out is NaN and
+ *   *status = KP_ERR_QP_FAIL.  KP_ERR_ARG beyond the limits above or when the window does not fit the step's LDS. */
+int kp_mpc_step_loaded(kp_mpc* mpc, const kp_basis* basis, int nw, int nobs, const double* zeta_win,
+                       const double* u_win, const double* what_prev, int flags, const double* zeta,
+                       const double* u_prev, const double* Yr, int iters, double* U_out, double* z_out,
+                       double* what_out, double* resnorm, int* status);
 /* The QP data (2H, f, A_ineq, b) of the most recent kp_mpc_step, for parity checks against
  * the literal assembly of Kmpc.m:861-883.  Hq: nvar x nvar, Aq: nrows x nvar (column-major). */
 int kp_mpc_last_qp(kp_mpc* mpc, double* Hq, double* f, double* Aq, double* bq);

@@ -62,6 +62,9 @@ struct kp_mpc {
   int* sb_col = nullptr;                        // ELL column table of a dense matrix: col[k * rows + r] = k
   size_t sb_cap = 0;                            // problems sb_A / sb_b are sized for
   double* sb_work = nullptr;                    // [sb_cap][nvar^2 + nvar + nrows]: H, f, b of every problem of a batch
+  // loaded steps: page-locked [observation window | estimate (nw) and resnorm] that the kernel reads and writes in place
+  double* h_ld = nullptr;
+  size_t h_ld_doubles = 0;
 };
 
 // ---- wave-level helpers (64 lanes): DPP inside 16-lane rows, v_readlane across the 4 rows ----
@@ -1019,10 +1022,247 @@ __host__ __device__ inline int mpc_lds_doubles(int N, int m, int Np, int nproj, 
          qp_lds_doubles(nvar, nrows);
 }
 
+// ---- loaded steps (kp_mpc_step_loaded): the load observer in front of the step ----------------------------------------
+// Kmpc.estimate_load_linear / _bilinear (Kmpc.m:1298-1356, :1360-1444) over a window of nobs past samples, then the loaded
+// lift z = [psi; w_1 psi; ...; w_nw psi] (Ksysid.m:1606-1612) of the current zeta.  The observer works in its own LDS block
+// behind the step's (offsets in doubles, each even):
+//   win: the staged window [(nobs + 1) x nzeta zeta rows | nobs x m inputs | nw previous estimate]
+//   fullc: dictionary columns of `chunk` window rows | psi: max(nobs, 1) x Nb | R: nobs x nz x (nw + 1) | d: nobs x nz
+//   M: (nw + 1)^2 normal matrix, q (nw + 1), d'd | QP: H nw^2, f, b, val, norm (2 nw each), col (2 nw ints), x (nw)
+//   xw: [1; w] | the QP solver's scratch
+#define KP_LOAD_MAX_NW 8
+#define KP_LOAD_MAX_NOBS 64
+#define KP_LOAD_FULL_CHUNK 4096   // doubles of dictionary columns evaluated per pass over the window rows
+struct LoadLayout {
+  int win, fullc, psi, R, d, M, H, f, b, val, norm, col, x, xw, qws, total, chunk;
+};
+__host__ __device__ inline int even_up(int n) { return (n + 1) & ~1; }
+__host__ __device__ inline LoadLayout load_layout(int nw, int nobs, int nzeta, int m, int nfull, int Nb) {
+  LoadLayout L;
+  const int nw1 = nw + 1, nr = 2 * nw;
+  L.chunk = nobs < 1 ? 1 : (KP_LOAD_FULL_CHUNK / nfull < 1 ? 1 : (KP_LOAD_FULL_CHUNK / nfull < nobs ? KP_LOAD_FULL_CHUNK / nfull : nobs));
+  int o = 0;
+  L.win = o; o += even_up((nobs + 1) * nzeta + nobs * m + nw);
+  L.fullc = o; o += even_up(L.chunk * nfull);
+  L.psi = o; o += even_up((nobs > 1 ? nobs : 1) * Nb);
+  L.R = o; o += even_up(nobs * nzeta * nw1);
+  L.d = o; o += even_up(nobs * nzeta);
+  L.M = o; o += even_up(nw1 * nw1 + nw1 + 1);
+  L.H = o; o += even_up(nw * nw);
+  L.f = o; o += even_up(nw);
+  L.b = o; o += even_up(nr);
+  L.val = o; o += even_up(nr);
+  L.norm = o; o += even_up(nr);
+  L.col = o; o += even_up((nr + 1) / 2);
+  L.x = o; o += even_up(nw);
+  L.xw = o; o += even_up(nw1 + 1);
+  L.qws = o; o += even_up(qp_lds_doubles(nw, nr));
+  L.total = o;
+  return L;
+}
+enum { KP_LOAD_RATE = 1, KP_LOAD_PIN_LAST = 2 };   // (the flags of kp_mpc_step_loaded)
+struct MpcLoadArgs {
+  int nw, nobs, flags, obs_off;   // obs_off: LDS offset (doubles) of the observer's block
+  const double* win;              // the window block in page-locked host memory (layout of `win` above)
+  double* out;                    // [nw] estimate | resnorm | 1 when the estimate failed, else 0  (page-locked host memory)
+};
+
+// one dictionary column of zeta: the evaluation of the fused lift in mpc_step_body, for the observer's window rows (the
+// unloaded instantiations keep their own copy of the loop, so that their code does not change)
+__device__ __forceinline__ double mpc_full_col(const BasisDev& b, const ColDesc& cd, const double* zeta) {
+  if (cd.kind == COL_MONO && b.nvars <= 8) {
+    int ex[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ex[i] = ((uint32_t)(i < 4 ? cd.aux : cd.pad) >> (8 * (i & 3))) & 0xff;
+    double v = 1.0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const double x = zeta[i < b.nvars ? i : 0];
+      for (int k = 0; k < ex[i]; ++k) v *= x;
+    }
+    return v;
+  }
+  return kp_eval_col(b, cd, zeta, 1);
+}
+// entry c of psi = econ_full(zeta) from its dictionary columns (dim_red: [zeta; pcs' full; 1], Ksysid.m:1521-1565)
+__device__ __forceinline__ double mpc_psi_entry(const BasisDev& b, const double* zeta, const double* full, int c) {
+  if (b.k_pcs == 0) return full[c];
+  if (c < b.nvars) return zeta[c];
+  if (c < b.nvars + b.k_pcs) {
+    const double* pc = b.pcs + (size_t)(c - b.nvars) * b.nfull;
+    double v = 0.0;
+    for (int i = 0; i < b.nfull; ++i) v += pc[i] * full[i];
+    return v;
+  }
+  return 1.0;
+}
+
+// The end of a loaded step whose estimate failed: the status word and, for a single zero-copy step, the release of the
+// spinning host thread (the same sequence as the end of mpc_step_body, which keeps its own copy so that the code of the
+// unloaded instantiations does not change).
+__device__ __forceinline__ void mpc_step_finish(const MpcArgs& a, int pb, int tid, int status, long long* stamps) {
+  if (tid == 0) a.status[pb] = status ? KP_ERR_QP_FAIL : KP_OK;
+  if (a.done_flag && pb == 0) {
+    __syncthreads();
+    if (tid == 0) {
+      __threadfence_system();
+      if (stamps) { a.done_flag[1] = (unsigned long long)stamps[0]; a.done_flag[2] = (unsigned long long)wall_clock64(); }
+      __threadfence_system();
+      __hip_atomic_store(&a.done_flag[0], a.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+
+// The load observer of a loaded step, by the whole workgroup (the window is in LDS at ob + L.win).  For past sample i with
+// psi_i = econ_full(zeta_i) the regression rows are R_i = G_i kron(I_{nw+1}, psi_i), G_i = A[:nz,:] (linear) or
+// A[:nz,:] + sum_j u_ij B_j[:nz,:] (bilinear): column l of R_i is the nz x Nb block l of G_i times psi_i, so no kron is
+// formed.  The right-hand sides are zeta_{i+1}[:nz] - B[:nz,:] u_i (linear) or zeta_{i+1}[:nz] (bilinear).  The normal
+// equations M = sum R_i'R_i, q = sum R_i'd_i give the lsqlin of Kmpc.m:1354 / :1442 as a QP in the free loads:
+// min ||R [1; w] - d||^2, -1 <= w <= 1 and, with KP_LOAD_RATE, |w - what_prev| <= 0.01; KP_LOAD_PIN_LAST pins the last
+// load to zero (the debugging equality Aeq = blkdiag(1, 0, 1) of Kmpc.m:1350).  Solved by wave 0 with the dual active-set
+// solver of kp_qp_solve (the host-assembled path's solver).  nobs = 0: no estimate, w = what_prev.
+// Writes [1; w] to xw (LDS), the estimate, the residual norm and the failure flag to la.out; returns true (uniform) when the
+// QP failed.
+__device__ __forceinline__ bool mpc_load_observer(const MpcArgs& a, const MpcLoadArgs& la, double* ob, double*& xw) {
+  const int tid = threadIdx.x;
+  const BasisDev& b = a.basis;
+  const int nw = la.nw, nobs = la.nobs, nz = b.nzeta, Nb = b.N, N = a.N, m = a.m, nw1 = nw + 1;
+  const LoadLayout L = load_layout(nw, nobs, nz, m, b.nfull, Nb);
+  const double* zw = ob + L.win;
+  const double* uw = zw + (nobs + 1) * nz;
+  const double* wprev = uw + nobs * m;
+  double* fullc = ob + L.fullc;
+  double* psi = ob + L.psi;
+  double* R = ob + L.R;
+  double* dv = ob + L.d;
+  double* Mq = ob + L.M;
+  xw = ob + L.xw;
+  if (nobs == 0) {
+    if (tid <= nw) xw[tid] = tid == 0 ? 1.0 : wprev[tid - 1];
+    if (tid < nw) la.out[tid] = wprev[tid];
+    if (tid == 0) { la.out[nw] = 0.0; la.out[nw + 1] = 0.0; }
+    wg_lds_barrier();
+    return false;
+  }
+  // psi of the first nobs window rows, `chunk` rows per pass
+  for (int r0 = 0; r0 < nobs; r0 += L.chunk) {
+    const int nr = min(L.chunk, nobs - r0);
+    for (int e = tid; e < nr * b.nfull; e += 256) {
+      const int i = e / b.nfull, c = e - i * b.nfull;
+      fullc[e] = mpc_full_col(b, b.cols[c], zw + (size_t)(r0 + i) * nz);
+    }
+    wg_lds_barrier();
+    for (int e = tid; e < nr * Nb; e += 256) {
+      const int i = e / Nb, c = e - i * Nb;
+      psi[(r0 + i) * Nb + c] = mpc_psi_entry(b, zw + (size_t)(r0 + i) * nz, fullc + i * b.nfull, c);
+    }
+    wg_lds_barrier();
+  }
+  // regression rows R[i][r][l] and right-hand sides d[i][r]
+  const bool bil = a.model_type == KP_MODEL_BILINEAR;
+  for (int e = tid; e < nobs * nz * nw1; e += 256) {
+    const int i = e / (nz * nw1), rem = e - i * nz * nw1, r = rem / nw1, l = rem - r * nw1;
+    const double* ps = psi + i * Nb;
+    const double* Ar = a.A + r + (size_t)l * Nb * N;
+    double s = 0.0;
+    for (int c = 0; c < Nb; ++c) s += Ar[(size_t)c * N] * ps[c];
+    if (bil)
+      for (int j = 0; j < m; ++j) {
+        const double* Br = a.B + r + ((size_t)j * N + (size_t)l * Nb) * N;
+        double t = 0.0;
+        for (int c = 0; c < Nb; ++c) t += Br[(size_t)c * N] * ps[c];
+        s += t * uw[i * m + j];
+      }
+    R[e] = s;
+  }
+  for (int e = tid; e < nobs * nz; e += 256) {
+    const int i = e / nz, r = e - i * nz;
+    double v = zw[(i + 1) * nz + r];
+    if (!bil) {
+      double s = 0.0;
+      for (int j = 0; j < m; ++j) s += a.B[r + (size_t)j * N] * uw[i * m + j];
+      v -= s;
+    }
+    dv[e] = v;
+  }
+  wg_lds_barrier();
+  // M (nw1 x nw1), q (nw1), d'd: 16 lanes per entry, summed by shuffles
+  const int nM = nw1 * nw1 + nw1 + 1, nt = nobs * nz;
+  for (int e16 = tid; e16 < nM * 16; e16 += 256) {
+    const int e = e16 >> 4, part = e16 & 15;
+    int c1, c2;   // columns of [R d] (nw1: d)
+    if (e < nw1 * nw1) { c1 = e % nw1; c2 = e / nw1; }
+    else if (e < nM - 1) { c1 = e - nw1 * nw1; c2 = nw1; }
+    else { c1 = nw1; c2 = nw1; }
+    double s = 0.0;
+    for (int t = part; t < nt; t += 16) {
+      const double x1 = c1 < nw1 ? R[t * nw1 + c1] : dv[t];
+      const double x2 = c2 < nw1 ? R[t * nw1 + c2] : dv[t];
+      s += x1 * x2;
+    }
+    s += __shfl_xor(s, 1, 64);
+    s += __shfl_xor(s, 2, 64);
+    s += __shfl_xor(s, 4, 64);
+    s += __shfl_xor(s, 8, 64);
+    if (part == 0) Mq[e] = s;
+  }
+  wg_lds_barrier();
+  // the QP in the free loads (w_0 .. w_{nf-1}; the pinned last one is 0)
+  const int nf = (la.flags & KP_LOAD_PIN_LAST) ? nw - 1 : nw;
+  double* H = ob + L.H;
+  double* f = ob + L.f;
+  double* bq = ob + L.b;
+  double* val = ob + L.val;
+  double* nrm = ob + L.norm;
+  int* col = (int*)(ob + L.col);
+  double* x = ob + L.x;
+  int* st_sh = (int*)(xw + nw1);
+  if (tid < 64) {
+    const int lane = tid;
+    for (int e = lane; e < nf * nf; e += 64) {
+      const int k1 = e % nf, k2 = e / nf;
+      H[e] = 2.0 * Mq[(k1 + 1) + (k2 + 1) * nw1];
+    }
+    const double* q = Mq + nw1 * nw1;
+    if (lane < nf) {
+      f[lane] = -2.0 * (q[lane + 1] - Mq[lane + 1]);     // -2 Rf'(d - R e_0)
+      double lo = -1.0, hi = 1.0;
+      if (la.flags & KP_LOAD_RATE) { lo = fmax(lo, wprev[lane] - 0.01); hi = fmin(hi, wprev[lane] + 0.01); }
+      val[2 * lane] = 1.0; col[2 * lane] = lane; nrm[2 * lane] = 1.0; bq[2 * lane] = hi;
+      val[2 * lane + 1] = -1.0; col[2 * lane + 1] = lane; nrm[2 * lane + 1] = 1.0; bq[2 * lane + 1] = -lo;
+    }
+    WSYNC();
+    int st = 0;
+    if (nf > 0) st = qp_goldfarb_idnani(H, f, EllMat{val, col, nrm, 1}, bq, nf, 2 * nf, ob + L.qws, x, 1e-10);
+    WSYNC();
+    if (lane <= nw) xw[lane] = lane == 0 ? 1.0 : (lane <= nf ? x[lane - 1] : 0.0);
+    WSYNC();
+    // resnorm = ||R [1; w] - d||^2, from the rows (the quadratic form in M, q, d'd would cancel)
+    double s = 0.0;
+    for (int t = lane; t < nt; t += 64) {
+      double r_ = 0.0;
+      for (int l = 0; l < nw1; ++l) r_ += R[t * nw1 + l] * xw[l];
+      r_ -= dv[t];
+      s += r_ * r_;
+    }
+    s = wave_sum(s);
+    if (lane < nw) la.out[lane] = st ? __builtin_nan("") : xw[lane + 1];
+    if (lane == 0) {
+      la.out[nw] = st ? __builtin_nan("") : s;
+      la.out[nw + 1] = st ? 1.0 : 0.0;
+      *st_sh = st;
+    }
+  }
+  wg_lds_barrier();
+  return *st_sh != 0;
+}
+
 // WARM: single-problem instantiation with the active-set warm start; the batched one carries none of that code
 // (its registers and branches cost the batch 1.8x when they were a run-time option).
-template <bool WARM>
-__device__ __forceinline__ void mpc_step_body(const MpcArgs& a) {
+// LOADED: the load observer and the loaded lift in front (kp_mpc_step_loaded, la != nullptr); the other instantiations
+// carry none of its code.
+template <bool WARM, bool LOADED = false>
+__device__ __forceinline__ void mpc_step_body(const MpcArgs& a, const MpcLoadArgs* la = nullptr) {
   extern __shared__ __align__(16) double sm[];
   const int tid = threadIdx.x;
   const int pb = blockIdx.x;
@@ -1069,6 +1309,13 @@ __device__ __forceinline__ void mpc_step_body(const MpcArgs& a) {
     const int bytes = w_ == 0 ? nzin * 8 : w_ == 1 ? nyr * 8 : w_ == 2 ? m * 8 : 0;
     for (int o = 0; o < bytes; o += 256)
       if (o + l4 < bytes) __builtin_amdgcn_global_load_lds((glb_char*)src + o + l4, (lds_char*)dst + o, 4, 0, 0);
+    if constexpr (LOADED) {   // the observation window by the fourth wave
+      const int wbytes = ((la->nobs + 1) * a.basis.nzeta + la->nobs * m + la->nw) * 8;
+      if (w_ == 3)
+        for (int o = 0; o < wbytes; o += 256)
+          if (o + l4 < wbytes)
+            __builtin_amdgcn_global_load_lds((glb_char*)la->win + o + l4, (lds_char*)(sm + la->obs_off) + o, 4, 0, 0);
+    }
   }
   const double r_diag = tid < nv ? a.r[tid % m] : 0.0;      // diagonal of R for the Hessian (element tid of its first round)
   const double r_bq0 = tid < nr ? a.bq0[tid] : 0.0;         // constant right-hand sides (first round of the loop below)
@@ -1135,7 +1382,24 @@ __device__ __forceinline__ void mpc_step_body(const MpcArgs& a) {
       }
     }
     if (stamps && tid == 0) stamps[10] = wall_clock64();      // host words and staged constants have landed
-  // ---- lifted state (Kmpc.m:842) ----
+  // ---- load estimate of the observation window (Kmpc.m:1298-1356 / :1360-1444) ----
+  double* xw = nullptr;   // [1; w]
+  bool obs_fail = false;
+  if constexpr (LOADED) {
+    obs_fail = mpc_load_observer(a, *la, sm + la->obs_off, xw);
+    if (obs_fail) {       // (uniform) the estimator's QP failed: NaN everywhere, as a failed step
+      for (int e = tid; e < nv; e += 256) a.U[(size_t)pb * nv + e] = __builtin_nan("");
+      if (a.z_out)
+        for (int c = tid; c < N; c += 256) a.z_out[(size_t)pb * N + c] = __builtin_nan("");
+      if (a.qp_export) {  // (state-bound steps: the generic QP kernel that follows sees NaN data, never a stale problem)
+        double* ex = a.qp_export + (size_t)pb * (nv * nv + nv + nr);
+        for (int e = tid; e < nv * nv + nv + nr; e += 256) ex[e] = __builtin_nan("");
+      }
+      mpc_step_finish(a, pb, tid, 1, stamps);
+      return;
+    }
+  }
+  // ---- lifted state (Kmpc.m:842; loaded: Kmpc.m:839-840, Ksysid.m:1606-1612) ----
   if (a.has_basis) {
     const BasisDev& b = a.basis;
     const double* zeta = z;
@@ -1160,19 +1424,30 @@ __device__ __forceinline__ void mpc_step_body(const MpcArgs& a) {
       full[c] = v;
     }
     wg_lds_barrier();
-    for (int c = tid; c < N; c += 256) {
-      double v;
-      if (b.k_pcs == 0)
-        v = full[c];
-      else if (c < b.nvars)
-        v = zeta[c];
-      else if (c < b.nvars + b.k_pcs) {
-        const double* pc = b.pcs + (size_t)(c - b.nvars) * b.nfull;
-        v = 0.0;
-        for (int i = 0; i < b.nfull; ++i) v += pc[i] * full[i];
-      } else
-        v = 1.0;
-      z[c] = v;
+    if constexpr (LOADED) {
+      const LoadLayout L = load_layout(la->nw, la->nobs, b.nzeta, m, b.nfull, b.N);
+      double* psi = sm + la->obs_off + L.psi;   // (the window's psi rows are dead)
+      for (int c = tid; c < b.N; c += 256) psi[c] = mpc_psi_entry(b, zeta, full, c);
+      wg_lds_barrier();
+      for (int c = tid; c < N; c += 256) {
+        const int l = c / b.N, j = c - l * b.N;
+        z[c] = l == 0 ? psi[j] : xw[l] * psi[j];
+      }
+    } else {
+      for (int c = tid; c < N; c += 256) {
+        double v;
+        if (b.k_pcs == 0)
+          v = full[c];
+        else if (c < b.nvars)
+          v = zeta[c];
+        else if (c < b.nvars + b.k_pcs) {
+          const double* pc = b.pcs + (size_t)(c - b.nvars) * b.nfull;
+          v = 0.0;
+          for (int i = 0; i < b.nfull; ++i) v += pc[i] * full[i];
+        } else
+          v = 1.0;
+        z[c] = v;
+      }
     }
   }
   wg_lds_barrier();
@@ -1517,6 +1792,10 @@ template <bool WARM>
 __global__ __launch_bounds__(256) void kp_mpc_step_kernel(MpcArgs a) {
   mpc_step_body<WARM>(a);
 }
+template <bool WARM>
+__global__ __launch_bounds__(256) void kp_mpc_step_loaded_kernel(MpcArgs a, MpcLoadArgs l) {
+  mpc_step_body<WARM, true>(a, &l);
+}
 __global__ __launch_bounds__(256, 4) void kp_mpc_step_batch_kernel(MpcArgs a) {
   mpc_step_body<false>(a);
 }
@@ -1539,6 +1818,7 @@ extern "C" int kp_mpc_destroy(kp_mpc* M) {
     if (p) (void)hipFree(p);
   if (M->h_in) (void)hipHostFree(M->h_in);
   if (M->h_out) (void)hipHostFree(M->h_out);
+  if (M->h_ld) (void)hipHostFree(M->h_ld);
   if (M->warm) (void)hipFree(M->warm);
   if (M->ellc) (void)hipFree(M->ellc);
   if (M->ellv) (void)hipFree(M->ellv);
@@ -1801,8 +2081,15 @@ extern "C" int kp_mpc_set_state_bounds(kp_mpc* M, int n, const double* lo, const
   return KP_OK;
 }
 
+// the observation window and outputs of a loaded step (kp_mpc_step_loaded)
+struct LoadIn {
+  int nw, nobs, flags;
+  const double *zeta_win, *u_win, *what_prev;
+  double *what_out, *resnorm;
+};
+
 static int mpc_run(kp_mpc* M, const kp_basis* basis, int nb, const double* z, const double* zeta, const double* u_prev,
-                   const double* Yr, int iters, double* U_out, double* z_out, int* status) {
+                   const double* Yr, int iters, double* U_out, double* z_out, int* status, const LoadIn* ld = nullptr) {
   kp_ctx* ctx = M->ctx;
   if (nb < 1 || !u_prev || !Yr || !U_out || iters < 1 || (!z && !zeta)) return ctx->fail(KP_ERR_ARG, "kp_mpc_step: bad argument");
   if (iters > 1 && M->model_type != KP_MODEL_BILINEAR) iters = 1;
@@ -1811,7 +2098,11 @@ static int mpc_run(kp_mpc* M, const kp_basis* basis, int nb, const double* z, co
   int nzeta = 0;
   if (zeta) {
     if (!basis) return ctx->fail(KP_ERR_ARG, "kp_mpc_step_zeta: basis required");
-    if (basis->dev.N != N || basis->dev.model_type == KP_MODEL_NONLINEAR)
+    if (ld) {
+      if (basis->dev.model_type == KP_MODEL_NONLINEAR || basis->dev.N * (ld->nw + 1) != N)
+        return ctx->fail(KP_ERR_ARG, "kp_mpc_step_loaded: the controller's width must be basis N * (nw + 1) = " +
+                                         std::to_string(basis->dev.N * (ld->nw + 1)) + ", it is " + std::to_string(N));
+    } else if (basis->dev.N != N || basis->dev.model_type == KP_MODEL_NONLINEAR)
       return ctx->fail(KP_ERR_ARG, "kp_mpc_step_zeta: basis does not match the controller's model");
     nzeta = basis->dev.nzeta;
   }
@@ -1916,6 +2207,35 @@ static int mpc_run(kp_mpc* M, const kp_basis* basis, int nb, const double* z, co
     a.done_seq = ++M->step_seq;
   }
   size_t lds = (size_t)mpc_lds_doubles(N, m, Np, nproj, nv, nr, (sb && iters > 1) ? 2 : iters, zeta ? basis->dev.nfull : 0) * 8 + 32;
+  MpcLoadArgs la{};
+  if (ld) {
+    // the observer's block behind the step's; the window goes to page-locked memory the kernel reads in place
+    const BasisDev& b = basis->dev;
+    const LoadLayout L = load_layout(ld->nw, ld->nobs, nzeta, m, b.nfull, b.N);
+    la.nw = ld->nw; la.nobs = ld->nobs; la.flags = ld->flags;
+    la.obs_off = (int)((lds / 8 + 1) & ~(size_t)1);
+    lds = (size_t)(la.obs_off + L.total) * 8;
+    if (lds > 160 * 1024)
+      return ctx->fail(KP_ERR_ARG, "kp_mpc_step_loaded: the observation window of " + std::to_string(ld->nobs) +
+                                       " samples exceeds the LDS budget (" + std::to_string(lds) + " bytes of 163840)");
+    const size_t nwin = (size_t)(ld->nobs + 1) * nzeta + (size_t)ld->nobs * m + ld->nw;
+    if (M->h_ld_doubles < nwin + ld->nw + 2) {
+      if (M->h_ld) (void)hipHostFree(M->h_ld);
+      M->h_ld = nullptr;
+      M->h_ld_doubles = 0;
+      KP_HIP(ctx, hipHostMalloc((void**)&M->h_ld, (nwin + ld->nw + 2) * 8, hipHostMallocDefault));
+      M->h_ld_doubles = nwin + ld->nw + 2;
+    }
+    double* w = M->h_ld;
+    if (ld->nobs > 0) {
+      memcpy(w, ld->zeta_win, (size_t)(ld->nobs + 1) * nzeta * 8);
+      memcpy(w + (size_t)(ld->nobs + 1) * nzeta, ld->u_win, (size_t)ld->nobs * m * 8);
+    }
+    double* wp = w + (size_t)(ld->nobs + 1) * nzeta + (size_t)ld->nobs * m;
+    for (int i = 0; i < ld->nw; ++i) wp[i] = ld->what_prev ? ld->what_prev[i] : 0.0;
+    la.win = w;
+    la.out = w + nwin;
+  }
   {
     // batched launches: the assembly's inputs inside the solver's scratch, no exchange words of the workgroup-wide solver
     const int n_asm = N + N * m + Np * nproj * m + (Np + 1) * nproj;
@@ -1932,17 +2252,26 @@ static int mpc_run(kp_mpc* M, const kp_basis* basis, int nb, const double* z, co
     a.stage_off = (int)((lds / 8 + 1) & ~(size_t)1);
     lds = (size_t)(a.stage_off + M->stage_doubles) * 8;
   }
-  static KpLdsCache step_lds[2];
+  static KpLdsCache step_lds[2], loaded_lds[2];
   const int wk = a.warm != nullptr;
   static KpLdsCache batch_lds;
   const bool bk = a.alias != 0;                       // the batched entry point
   if (bk) KP_HIP(ctx, kp_ensure_lds(batch_lds, (const void*)kp_mpc_step_batch_kernel, lds));
+  else if (ld)
+    KP_HIP(ctx, kp_ensure_lds(loaded_lds[wk], wk ? (const void*)kp_mpc_step_loaded_kernel<true> : (const void*)kp_mpc_step_loaded_kernel<false>, lds));
   else KP_HIP(ctx, kp_ensure_lds(step_lds[wk], wk ? (const void*)kp_mpc_step_kernel<true> : (const void*)kp_mpc_step_kernel<false>, lds));
+  // one launch of the single-problem step kernel (loaded steps: with the observer in front)
+  auto launch_step = [&]() {
+    if (ld) {
+      if (wk) hipLaunchKernelGGL(kp_mpc_step_loaded_kernel<true>, dim3(nb), dim3(256), lds, ctx->stream, a, la);
+      else hipLaunchKernelGGL(kp_mpc_step_loaded_kernel<false>, dim3(nb), dim3(256), lds, ctx->stream, a, la);
+    } else if (wk) hipLaunchKernelGGL(kp_mpc_step_kernel<true>, dim3(nb), dim3(256), lds, ctx->stream, a);
+    else hipLaunchKernelGGL(kp_mpc_step_kernel<false>, dim3(nb), dim3(256), lds, ctx->stream, a);
+  };
   if (!spin) KP_HIP(ctx, hipEventRecord(ctx->evp[4], ctx->stream));
   if (!sb) {
     if (bk) hipLaunchKernelGGL(kp_mpc_step_batch_kernel, dim3(nb), dim3(256), lds, ctx->stream, a);
-    else if (wk) hipLaunchKernelGGL(kp_mpc_step_kernel<true>, dim3(nb), dim3(256), lds, ctx->stream, a);
-    else hipLaunchKernelGGL(kp_mpc_step_kernel<false>, dim3(nb), dim3(256), lds, ctx->stream, a);
+    else launch_step();
     KP_HIP(ctx, hipGetLastError());
   } else {
     // Every pass: the step kernel assembles H, f (along the lifted horizon of the previous pass's inputs from pass 2 on,
@@ -1959,8 +2288,7 @@ static int mpc_run(kp_mpc* M, const kp_basis* basis, int nb, const double* z, co
     EllMat E{M->sb_A, M->sb_col, nrm, nv};
     for (int pass = 0; pass < iters; ++pass) {
       a.U_lin = pass > 0 ? dx : nullptr;
-      if (wk) hipLaunchKernelGGL(kp_mpc_step_kernel<true>, dim3(nb), dim3(256), lds, ctx->stream, a);
-      else hipLaunchKernelGGL(kp_mpc_step_kernel<false>, dim3(nb), dim3(256), lds, ctx->stream, a);
+      launch_step();
       KP_HIP(ctx, hipGetLastError());
       if (pass == 0) {
         hipLaunchKernelGGL(kp_mpc_sb_kernel, dim3(nb), dim3(256), (size_t)(N * m + N) * 8, ctx->stream, M->model_type, N, m, Np, nv, nr, M->sb_n,
@@ -1999,6 +2327,16 @@ static int mpc_run(kp_mpc* M, const kp_basis* basis, int nb, const double* z, co
       for (int i = 0; i < m; ++i) U_out[(size_t)p * nv + (size_t)i * Np + j] = x[(size_t)p * nv + j * m + i];
     if (status) status[p] = st[p];
   }
+  if (ld) {
+    if (ld->what_out) memcpy(ld->what_out, la.out, (size_t)ld->nw * 8);
+    if (ld->resnorm) *ld->resnorm = la.out[ld->nw];
+    // a failed estimate fails the step whatever path solved it (the state-bound passes run on the NaN state the kernel
+    // exported and would report their own status)
+    if (la.out[ld->nw + 1] != 0.0) {
+      for (int i = 0; i < nv; ++i) U_out[i] = std::nan("");
+      if (status) status[0] = KP_ERR_QP_FAIL;
+    }
+  }
   float ms = 0;
   if (spin) ctx->timers[2] = (double)(M->h_flag[2] - M->h_flag[1]) * 1e-5;        // wall_clock64 ticks of 10 ns -> ms
   else if (hipEventElapsedTime(&ms, ctx->evp[4], ctx->evp[5]) == hipSuccess) ctx->timers[2] = ms;
@@ -2015,6 +2353,24 @@ extern "C" int kp_mpc_step_zeta(kp_mpc* M, const kp_basis* basis, const double* 
                                 int iters, double* U_out, double* z_out, int* status) {
   if (!M) return KP_ERR_ARG;
   return mpc_run(M, basis, 1, nullptr, zeta, u_prev, Yr, iters, U_out, z_out, status);
+}
+
+extern "C" int kp_mpc_step_loaded(kp_mpc* M, const kp_basis* basis, int nw, int nobs, const double* zeta_win, const double* u_win,
+                                  const double* what_prev, int flags, const double* zeta, const double* u_prev, const double* Yr,
+                                  int iters, double* U_out, double* z_out, double* what_out, double* resnorm, int* status) {
+  if (!M) return KP_ERR_ARG;
+  kp_ctx* ctx = M->ctx;
+  if (!basis || !zeta) return ctx->fail(KP_ERR_ARG, "kp_mpc_step_loaded: basis and zeta are required");
+  if (nw < 1 || nw > KP_LOAD_MAX_NW)
+    return ctx->fail(KP_ERR_ARG, "kp_mpc_step_loaded: nw = " + std::to_string(nw) + " outside 1 .. " + std::to_string(KP_LOAD_MAX_NW));
+  if (nobs < 0 || nobs > KP_LOAD_MAX_NOBS)
+    return ctx->fail(KP_ERR_ARG, "kp_mpc_step_loaded: nobs = " + std::to_string(nobs) + " outside 0 .. " + std::to_string(KP_LOAD_MAX_NOBS));
+  if (flags & ~(KP_LOAD_RATE | KP_LOAD_PIN_LAST)) return ctx->fail(KP_ERR_ARG, "kp_mpc_step_loaded: unknown flags");
+  if (nobs > 0 && (!zeta_win || !u_win)) return ctx->fail(KP_ERR_ARG, "kp_mpc_step_loaded: nobs > 0 needs zeta_win and u_win");
+  if ((nobs == 0 || (flags & KP_LOAD_RATE)) && !what_prev)
+    return ctx->fail(KP_ERR_ARG, "kp_mpc_step_loaded: what_prev is required with nobs = 0 or KP_LOAD_RATE");
+  const LoadIn ld{nw, nobs, flags, zeta_win, u_win, what_prev, what_out, resnorm};
+  return mpc_run(M, basis, 1, nullptr, zeta, u_prev, Yr, iters, U_out, z_out, status, &ld);
 }
 
 extern "C" int kp_mpc_step_batch(kp_mpc* M, int nb, const double* z, const double* u_prev, const double* Yr, double* U_out,

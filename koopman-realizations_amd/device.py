@@ -565,6 +565,27 @@ class Mpc:
             F.check(rc, self.ctx.handle)
         return Ub.copy(order="F"), zo.copy(), st.value
 
+    LOAD_RATE, LOAD_PIN_LAST = 1, 2      # flags of kp_mpc_step_loaded
+
+    def step_loaded(self, basis: Basis, nw, zeta_win, u_win, what_prev, flags, zeta, u_prev, Yr, iters=1):
+        """kp_mpc_step_loaded: the load observer over the window (zeta_win: nobs + 1 rows, u_win: nobs rows; nobs = 0
+        lifts with what_prev), the loaded lift of zeta and the step, one launch.  Returns (U, z, what, resnorm, status)."""
+        nw = int(nw)
+        zw = np.ascontiguousarray(np.atleast_2d(zeta_win) if np.size(zeta_win) else np.zeros((1, basis.nzeta)), dtype=np.float64)
+        nobs = zw.shape[0] - 1
+        uw = np.ascontiguousarray(np.asarray(u_win, dtype=np.float64).reshape(nobs, self.m))
+        wp = None if what_prev is None else np.ascontiguousarray(np.ravel(what_prev), dtype=np.float64)
+        if wp is not None and wp.size != nw:
+            raise ValueError(f"what_prev must have nw = {nw} entries")
+        z = np.ascontiguousarray(zeta, dtype=np.float64); up = np.ascontiguousarray(u_prev, dtype=np.float64)
+        yr = np.ascontiguousarray(Yr, dtype=np.float64)
+        U = np.zeros((self.Np, self.m), order="F"); zo = np.zeros(self.N); what = np.zeros(nw)
+        rn = C.c_double(); st = C.c_int()
+        F.check(F.lib().kp_mpc_step_loaded(self._h, basis._h, nw, nobs, F.dptr(zw), F.dptr(uw), F.dptr(wp), int(flags),
+                                           F.dptr(z), F.dptr(up), F.dptr(yr), int(iters), F.dptr(U), F.dptr(zo),
+                                           F.dptr(what), C.byref(rn), C.byref(st)), self.ctx.handle)
+        return U, zo, what, rn.value, st.value
+
     def step_batch(self, Z, U_prev, YR):
         """Z (nb,N), U_prev (nb,m), YR (nb, nproj*(Np+1)) -> U (nb, Np, m), status (nb,)."""
         Z = np.ascontiguousarray(Z, dtype=np.float64); UP = np.ascontiguousarray(U_prev, dtype=np.float64)

@@ -6,6 +6,8 @@ lift, QP assembly and QP solve — is one kernel launch in libkoopman_hip.so.
 Loaded models (sysid_class.loaded): the lifted state is the loaded lift with the current load estimate
 traj['what'] (Kmpc.m:347-348, :771-772, :839-840); estimate_load_linear / estimate_load_bilinear (Kmpc.m:1298-1445)
 assemble the regression on the host and solve the constrained least squares with the library's QP kernel.
+get_mpcInput_loaded does the estimate, the loaded lift and the step in one launch (kp_mpc_step_loaded); a loaded Ksim
+uses it when fused_load_step is true (the default) and the host-assembled estimate + step otherwise.
 state_bounds (Kmpc.m:300-318) are scaled down like the reference does and handed to kp_mpc_set_state_bounds.
 Out of scope: mpc_type 'nonlinear' (fmincon SQP).
 """
@@ -41,6 +43,9 @@ class Kmpc:
         self.cost_terminal = 100.0
         self.cost_input = 0.0
         self.projmtx = self.model["C"]
+        self.load_obs_horizon = 10                  # :66-67 (loaded models: past samples of the load observer's window)
+        self.load_obs_period = 1                    # (steps between load estimates)
+        self.fused_load_step = True                 # Ksim: estimate + lift + step in one launch (get_mpcInput_loaded)
         self.mpc_type = "nonlinear" if self.model_type == "nonlinear" else "linear"
         for k, v in kwargs.items():                 # parse_args :107-113
             if not hasattr(self, k):
@@ -179,6 +184,38 @@ class Kmpc:
         rhs = [zp[i + 1, :nz] for i in range(len(G))]
         return self._lsqlin_load(np.vstack(rows), np.concatenate(rhs), whatpast, False)
 
+    def get_mpcInput_loaded(self, traj, ref, ypast, upast, estimate=True, whatpast=None, iters=1):
+        """One step of a loaded controller with the load observer fused in (kp_mpc_step_loaded): with `estimate`, the
+        estimate_load_linear / _bilinear of the window (ypast, upast) (Kmpc.m:1298-1444; whatpast adds the rate rows),
+        else the lift uses traj['what'] as it is; then the loaded lift and get_mpcInput / get_mpcInput_bilinear_iter(.., iters)
+        (Kmpc.m:329-387, :817-904), state bounds included.  Returns (U, z, what) with `what` scaled down; the residual norm of the estimate is
+        kept in self.last_resnorm."""
+        if not self.loaded:
+            raise ValueError("get_mpcInput_loaded needs a loaded model")
+        p = self.params; nw, nd, m = p["nw"], p["nd"], p["m"]
+        zeta = self._zeta(traj)
+        u_prev = np.atleast_2d(traj["u"])[-1]
+        flags = 0
+        if estimate:
+            ypast = np.atleast_2d(ypast); upast = np.atleast_2d(upast)
+            if ypast.shape[0] != upast.shape[0]:
+                raise ValueError("Input arguments must have the same number of rows")
+            _, zwin = self.sysid.get_zeta({"y": ypast, "u": upast})
+            nobs = zwin.shape[0] - 1
+            # the input of past sample i as the reference indexes it: upast(nd + i) (linear, Kmpc.m:1328-1335), upast(i) (bilinear, :1388-1393)
+            uwin = upast[nd:nd + nobs] if self.model_type == "linear" else upast[:nobs]
+            wprev = None if whatpast is None else np.atleast_2d(whatpast)[-1]
+            if wprev is not None:
+                flags |= Mpc.LOAD_RATE
+            if self.model_type == "linear" and nw == 2:
+                flags |= Mpc.LOAD_PIN_LAST
+        else:
+            zwin, uwin, wprev = np.zeros((1, p["nzeta"])), np.zeros((0, m)), np.atleast_2d(traj["what"])[-1]
+        U, z, what, rn, st = self.dev.step_loaded(self.sysid.basis_dev, nw, zwin, uwin, wprev, flags, zeta, u_prev,
+                                                  self._pad_ref(ref), int(iters))
+        self.last_resnorm = rn
+        return U, z, what
+
     def get_mpcInput(self, traj, ref):
         """Kmpc.m:329-387 (linear model)."""
         return self._step(traj, ref, 1)
@@ -233,39 +270,111 @@ class Ksim:
         self.sys = system_class
         self.mpc = mpc_class
 
-    def run_trial_mpc(self, ref, x0=None, u0=None):
-        """Ksim.m:47-262 (delays = 0, unloaded).  Result fields as in the reference."""
+    def _load_rows(self, load_value, nref, check_width):
+        """Ksim.m:79-104: the load of every step, or the reference's error for a wrong shape."""
+        lv = np.asarray(load_value, dtype=np.float64)
+        lv = lv.reshape(1, -1) if lv.ndim <= 1 else lv
+        if check_width:
+            nw = int(self.sys.params.get("nw", self.mpc.params["nw"]))
+            if lv.shape[1] != nw:
+                raise ValueError(f"Load argument should have {nw} columns, not {lv.shape[1]}")
+            if lv.size == 0:
+                return np.zeros((nref, nw))
+        if lv.shape[0] == 1:                                                  # constant load
+            return np.tile(lv, (nref, 1))
+        if lv.shape[0] != nref:
+            raise ValueError("Load argument must have 1 or the same number of rows as ref argument")
+        return lv
+
+    def run_trial_mpc(self, ref, x0=None, u0=None, load_value=None):
+        """Ksim.m:47-262: the closed loop of the controller and the plant over the reference `ref` (rows: samples).
+        x0, u0: the initial state and input, held over the nd + 1 rows of the delayed history (:63-76); the controller
+        sees the last nd + 1 outputs and inputs (:153-166).  load_value: the true load of the plant, one row (constant)
+        or one row per row of ref (:79-104); a loaded model requires it.  Loaded models estimate the load every
+        load_obs_period steps over the last load_obs_horizon + 1 samples (:169-194) and lift with the estimate; with
+        mpc.fused_load_step the estimate, lift and step are one launch, otherwise the host assembles the estimate.
+        The plant steps with the load of the sample the step starts from (results W, row k - 1 in 0-based rows).
+        Result fields as in the reference (What: the scaled-up estimates, a zero first row).  comp_time: the reference's
+        tic (Ksim.m:205) comes after the load estimate; the host-assembled path times the same span, the fused path's time
+        includes the estimate, which runs inside the same launch - the two paths' comp_time measure different work."""
         mpc, s = self.mpc, self.mpc.sysid
-        Np = mpc.horizon
+        Np, nd = mpc.horizon, int(mpc.params["nd"])
         nx, nu = int(self.sys.params["nx"]), int(self.sys.params["nu"])
-        x0 = np.zeros(nx) if x0 is None else np.asarray(x0, dtype=np.float64)
-        u0 = np.zeros(nu) if u0 is None else np.asarray(u0, dtype=np.float64)
-        y0 = np.asarray(self.sys.get_y(x0), dtype=np.float64)
         ref = np.atleast_2d(np.asarray(ref, dtype=np.float64))
+        nref = ref.shape[0]
+        x0 = np.zeros((nd + 1, nx)) if x0 is None else np.tile(np.asarray(x0, dtype=np.float64).ravel(), (nd + 1, 1))
+        u0 = np.zeros((nd + 1, nu)) if u0 is None else np.tile(np.asarray(u0, dtype=np.float64).ravel(), (nd + 1, 1))
+        y0 = np.array([np.asarray(self.sys.get_y(x), dtype=np.float64) for x in x0])
+        w = None
+        if mpc.loaded:
+            if load_value is None:
+                raise ValueError("Missing argument: The model expects a load condition but none was provided")
+            w = self._load_rows(load_value, nref, True)
+        elif load_value is not None:                    # the model has no load, the plant carries one
+            w = self._load_rows(load_value, nref, False)
         ref_sc = mpc.scaledown_ref(ref)                                       # Ksim.m:113
-        res = {"T": [0.0], "U": [u0], "Y": [y0], "K": [0], "R": [ref[0]], "X": [x0], "Z": [], "comp_time": [], "err": []}
+        res = {"T": [0.0], "U": [u0[-1]], "Y": [y0[-1]], "K": [0], "R": [ref[0]], "X": [x0[-1]], "Z": [], "comp_time": [],
+               "err": []}
+        if mpc.loaded:
+            res["What"] = [np.zeros(w.shape[1])]                              # :139-144
         proj = mpc.projmtx[:, :mpc.params["n"]]
+        Ho, period = int(mpc.load_obs_horizon), int(mpc.load_obs_period)
         k = 1
         while k < ref_sc.shape[0]:                                            # :147
-            cur = {"y": s.scaledown_y(res["Y"][-1])[None, :], "u": s.scaledown_u(res["U"][-1])[None, :]}   # :153-166
-            refhor = ref_sc[k - 1:k + Np]                                     # :198-202 (1-based k : k+Np)
-            t0 = time.perf_counter()                                          # :205
-            if mpc.model_type == "linear":
-                U, z = mpc.get_mpcInput(cur, refhor)
+            if k == 1:                                                        # :153-166
+                cy, cu = y0, u0
+            elif k < nd + 1:
+                cy, cu = np.vstack([y0[k - 1:-1], res["Y"]]), np.vstack([u0[k - 1:-1], res["U"]])
             else:
-                U, z = mpc.get_mpcInput_bilinear_iter(cur, refhor, 1)         # :210
-            comp = time.perf_counter() - t0
+                cy, cu = np.array(res["Y"][-(nd + 1):]), np.array(res["U"][-(nd + 1):])
+            cur = {"y": s.scaledown_y(cy), "u": s.scaledown_u(cu)}
+            refhor = ref_sc[k - 1:k + Np]                                     # :198-202 (1-based k : k+Np)
+            if mpc.loaded:                                                    # :169-194
+                if k < nd + 2:                                                # minimum size nd + 2
+                    yp, up = np.tile(s.scaledown_y(y0), (nd + 2, 1)), np.tile(s.scaledown_u(u0), (nd + 2, 1))
+                elif k < Ho + 1:
+                    yp = s.scaledown_y(np.vstack([y0[k - 1:-1], res["Y"]]))
+                    up = s.scaledown_u(np.vstack([u0[k - 1:-1], res["U"]]))
+                else:
+                    yp, up = s.scaledown_y(np.array(res["Y"][-(Ho + 1):])), s.scaledown_u(np.array(res["U"][-(Ho + 1):]))
+                estimate = k % period == 0
+                if not estimate:
+                    cur["what"] = s.scaledown_w(res["What"][-1])
+                if mpc.fused_load_step:
+                    t0 = time.perf_counter()
+                    U, z, what = mpc.get_mpcInput_loaded(cur, refhor, yp, up, estimate=estimate)
+                    comp = time.perf_counter() - t0
+                    cur["what"] = what
+                else:
+                    if estimate:
+                        est = mpc.estimate_load_linear if mpc.model_type == "linear" else mpc.estimate_load_bilinear
+                        cur["what"] = est(yp, up)[0]
+                    t0 = time.perf_counter()
+                    U, z = mpc._step(cur, refhor, 1)
+                    comp = time.perf_counter() - t0
+                res["What"].append(s.scaleup_w(cur["what"]))
+            else:
+                t0 = time.perf_counter()                                      # :205
+                if mpc.model_type == "linear":
+                    U, z = mpc.get_mpcInput(cur, refhor)
+                else:
+                    U, z = mpc.get_mpcInput_bilinear_iter(cur, refhor, 1)     # :210
+                comp = time.perf_counter() - t0
             if np.isnan(U).any():                                             # :220-222
                 break
             u_kp1 = s.scaleup_u(U[1])                                         # :225-228
-            x_kp1 = np.asarray(self.sys.simulate_Ts(res["X"][-1], res["U"][-1], None), dtype=np.float64)   # :239-245
+            w_k = None if w is None else w[k - 1]                             # :239-245 results.W(k,:), 1-based k
+            x_kp1 = np.asarray(self.sys.simulate_Ts(res["X"][-1], res["U"][-1], w_k), dtype=np.float64)
             y_kp1 = np.asarray(self.sys.get_y(x_kp1), dtype=np.float64)
             res["T"].append(k * mpc.params["Ts"]); res["U"].append(u_kp1); res["Y"].append(y_kp1); res["K"].append(k)
             res["R"].append(mpc.scaleup_ref(ref_sc[k - 1])[0]); res["X"].append(x_kp1); res["Z"].append(z)
             res["comp_time"].append(comp)
             res["err"].append(float(np.sqrt(((res["R"][-1] - proj @ y_kp1) ** 2).sum())))   # :258
             k += 1
-        return {k_: np.array(v) for k_, v in res.items()}
+        out = {k_: np.array(v) for k_, v in res.items()}
+        if w is not None:
+            out["W"] = w
+        return out
 
 
 class ModelPlant:

@@ -57,6 +57,10 @@
  *             kp_mex('mpc_set_state_bounds', m, lo, hi)    kp_mex('mpc_destroy', m)    d = kp_mex('mpc_dims', m)   [nvar nrows]
  *             [U, z] = kp_mex('mpc_step_zeta', m, b, zeta, u_prev, Yr [, iters])   U is NaN when the QP failed   kp_mpc_step_zeta
  *             U = kp_mex('mpc_step', m, z, u_prev, Yr [, iters])                                           kp_mpc_step
+ *             [U, z, what, resnorm] = kp_mex('mpc_step', m, zeta, u_prev, Yr, iters, b, nw, Zwin, Uwin, what_prev, flags)
+ *                                                          loaded model: load estimate + loaded lift + step    kp_mpc_step_loaded
+ *                                                          Zwin nzeta x (nobs + 1), Uwin m x nobs (both empty: no estimate,
+ *                                                          lift with what_prev), what_prev nw or [], flags 1 rate rows, 2 pin last
  *             [U, status] = kp_mex('mpc_step_batch', m, Z, Uprev, YR)    Z N x nb, ..., U Np x m x nb      kp_mpc_step_batch
  *             [Hq, f, Aq, bq] = kp_mex('mpc_last_qp', m)     [us, counts] = kp_mex('mpc_last_profile', m)
  *             us16 = kp_mex('mpc_last_stamps', m)
@@ -806,13 +810,44 @@ static void c_mpc_step_zeta(ARGS) {
 static void c_mpc_step(ARGS) {
   UNUSED;
   /* the step from an already lifted state (loaded models lift with the current load estimate on the host side of the
-   * boundary, Kmpc.m:347-348) */
+   * boundary, Kmpc.m:347-348), or with the trailing arguments the loaded step with its load observer */
   kp_mpc* mp = (kp_mpc*)get_handle(prhs[1], H_MPC);
   int nvar, nrows, status = 0;
   check(kp_mpc_dims(mp, &nvar, &nrows), NULL);
   const int m = (int)mxGetNumberOfElements(prhs[3]);
   if (m < 1 || nvar % m) mexErrMsgIdAndTxt("kp:size", "mpc_step: u_prev must have m entries");
   const int Np = nvar / m;
+  if (nrhs <= 6 && nlhs > 2) mexErrMsgIdAndTxt("kp:usage", "kp_mex('mpc_step', ...): at most 2 outputs without the loaded arguments");
+  if (nrhs > 6) {
+    /* loaded form: the load observer over the window, the loaded lift of zeta and the step in one call (Ksim.m:169-194) */
+    if (nrhs != 12) mexErrMsgIdAndTxt("kp:usage", "mpc_step: the loaded form takes b, nw, Zwin, Uwin, what_prev, flags after iters");
+    kp_basis* b = (kp_basis*)get_handle(prhs[6], H_BASIS);
+    int nv, nf, N, W;
+    basis_wn(b, NULL, &nv, &nf, &N, &W);
+    const int nw = int_arg(prhs[7], "nw");
+    if (nw < 1) mexErrMsgIdAndTxt("kp:size", "mpc_step: nw must be at least 1");
+    if ((int)mxGetNumberOfElements(prhs[2]) != nv) mexErrMsgIdAndTxt("kp:size", "mpc_step: zeta must have %d entries", nv);
+    if (mxGetNumberOfElements(prhs[4]) % (size_t)(Np + 1)) mexErrMsgIdAndTxt("kp:size", "mpc_step: Yr must have nproj (Np + 1) entries");
+    const int nobs = mxIsEmpty(prhs[8]) ? 0 : (int)mxGetN(prhs[8]) - 1;
+    if (nobs > 0 && (int)mxGetM(prhs[8]) != nv) mexErrMsgIdAndTxt("kp:size", "mpc_step: Zwin must be nzeta = %d x (nobs + 1)", nv);
+    if (nobs == 0 && !mxIsEmpty(prhs[8]) && (int)mxGetNumberOfElements(prhs[8]) != nv)
+      mexErrMsgIdAndTxt("kp:size", "mpc_step: Zwin must be nzeta = %d x (nobs + 1)", nv);
+    if ((int)mxGetNumberOfElements(prhs[9]) != nobs * m || (nobs > 0 && (int)mxGetM(prhs[9]) != m))
+      mexErrMsgIdAndTxt("kp:size", "mpc_step: Uwin must be m = %d x nobs = %d", m, nobs);
+    if (!mxIsEmpty(prhs[10]) && (int)mxGetNumberOfElements(prhs[10]) != nw)
+      mexErrMsgIdAndTxt("kp:size", "mpc_step: what_prev must have nw = %d entries", nw);
+    mxArray* z = mxCreateDoubleMatrix((mwSize)N * (nw + 1), 1, mxREAL);
+    mxArray* what = mxCreateDoubleMatrix(nw, 1, mxREAL);
+    double resnorm = 0.0;
+    plhs[0] = mxCreateDoubleMatrix(Np, m, mxREAL);
+    check(kp_mpc_step_loaded(mp, b, nw, nobs, dbl(prhs[8]), dbl(prhs[9]), dbl(prhs[10]), int_arg(prhs[11], "flags"), dbl(prhs[2]),
+                             dbl(prhs[3]), dbl(prhs[4]), int_arg(prhs[5], "iters"), mxGetPr(plhs[0]), mxGetPr(z), mxGetPr(what),
+                             &resnorm, &status), NULL);
+    set_or_drop(nlhs, plhs, 1, z);
+    set_or_drop(nlhs, plhs, 2, what);
+    set_or_drop(nlhs, plhs, 3, mxCreateDoubleScalar(resnorm));
+    return;
+  }
   plhs[0] = mxCreateDoubleMatrix(Np, m, mxREAL);
   check(kp_mpc_step(mp, dbl(prhs[2]), dbl(prhs[3]), dbl(prhs[4]), nrhs > 5 ? int_arg(prhs[5], "iters") : 1, mxGetPr(plhs[0]), &status), NULL);
   set_or_drop(nlhs, plhs, 1, mxCreateDoubleScalar(status));
@@ -1114,7 +1149,7 @@ static const kp_command g_commands[] = {
   {"traj_scale", 1, 1, 1, c_traj_scale}, {"sweep_eval", 4, 4, 3, c_sweep_eval}, {"sweep_eval_nested", 5, 5, 2, c_sweep_eval_nested},
   {"sweep_nested_get_K", 6, 6, 1, c_sweep_nested_get_K},
   {"mpc_create", 13, 13, 1, c_mpc_create}, {"mpc_set_state_bounds", 3, 3, 0, c_mpc_set_state_bounds}, {"mpc_destroy", 1, 1, 0, c_mpc_destroy},
-  {"mpc_dims", 1, 1, 1, c_mpc_dims}, {"mpc_step_zeta", 5, 6, 2, c_mpc_step_zeta}, {"mpc_step", 4, 5, 2, c_mpc_step},
+  {"mpc_dims", 1, 1, 1, c_mpc_dims}, {"mpc_step_zeta", 5, 6, 2, c_mpc_step_zeta}, {"mpc_step", 4, 11, 4, c_mpc_step},
   {"mpc_step_batch", 4, 4, 2, c_mpc_step_batch}, {"mpc_last_qp", 1, 1, 4, c_mpc_last_qp}, {"mpc_last_profile", 1, 1, 2, c_mpc_last_profile},
   {"mpc_last_stamps", 1, 1, 1, c_mpc_last_stamps},
   {"qp_solve", 5, 5, 2, c_qp_solve},
