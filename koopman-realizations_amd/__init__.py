@@ -9,7 +9,7 @@ name carries a hyphen to match the reference's repository name).
 from . import _ffi
 from ._ffi import KoopmanHipError
 from .device import Basis, Context, Snapshots, fit, fit_gram, fit_gram_sharded, fit_refine, fit_sharded
-from .device import Mpc
+from .device import Mpc, Nmpc
 from . import comm
 from .multi import Multi, MultiMpc
 from .arm import Arm

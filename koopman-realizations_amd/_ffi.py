@@ -123,6 +123,20 @@ SIGNATURES = {
     "kp_multi_mpc_step_batch": (C.c_int, [vp, C.c_int, c_dp, c_dp, c_dp, c_dp, c_ip]),
 }
 
+# the nonlinear MPC entry points (include/koopman_hip_nmpc.h)
+NMPC_SIGNATURES = {
+    "kp_lift_jacobian": (C.c_int, [vp, vp, C.c_int, c_dp, c_dp]),
+    "kp_nmpc_create": (C.c_int, [vp, vp, c_dp, C.c_int, c_dp, C.c_int, C.c_double, C.c_double, c_dp, c_dp, c_dp,
+                                 C.c_double, C.c_double, C.POINTER(vp)]),
+    "kp_nmpc_set_state_bounds": (C.c_int, [vp, C.c_int, c_dp, c_dp]),
+    "kp_nmpc_set_options": (C.c_int, [vp, C.c_int, C.c_double, C.c_double, C.c_double]),
+    "kp_nmpc_dims": (C.c_int, [vp, c_ip, c_ip]),
+    "kp_nmpc_step": (C.c_int, [vp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_ip]),
+    "kp_nmpc_step_batch": (C.c_int, [vp, C.c_int, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_ip]),
+    "kp_nmpc_last_jacobians": (C.c_int, [vp, c_dp]),
+    "kp_nmpc_destroy": (C.c_int, [vp]),
+}
+
 _lib = None
 
 
@@ -134,7 +148,7 @@ def lib():
             raise OSError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(make -C koopman-realizations_amd/csrc)")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in (SIGNATURES | NMPC_SIGNATURES).items():
             fn = getattr(l, name)
             fn.restype, fn.argtypes = res, args
         _lib = l

@@ -218,6 +218,15 @@ class Context:
         F.check(F.lib().kp_rollout_nl(self._h, basis.handle, 1, F.dptr(Kf), F.dptr(z0), F.dptr(U), T, F.dptr(Z)), self._h)
         return Z
 
+    def lift_jacobian(self, basis, V):
+        """kp_lift_jacobian: d econ_full / dv at the rows of V (rows x nvars; v = [zeta, u] for a nonlinear dictionary)
+        -> (rows, N, nvars)."""
+        V = F.fcol(np.atleast_2d(V))
+        rows = V.shape[0]
+        J = np.zeros((rows, basis.nvars, basis.N))          # per row an N x nvars column-major block
+        F.check(F.lib().kp_lift_jacobian(self._h, basis.handle, rows, F.dptr(V), F.dptr(J)), self._h)
+        return np.transpose(J, (0, 2, 1))
+
     def qp_solve(self, H, f, A, b):
         """quadprog_gurobi(H,f,A,b) shim: NaN vector on failure (quadprog_gurobi.m:22-23)."""
         H = F.fcol(H); A = F.fcol(A)
@@ -607,6 +616,100 @@ class Mpc:
     def close(self):
         if self._h:
             F.lib().kp_mpc_destroy(self._h)
+            self._h = F.vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Nmpc:
+    """kp_nmpc: the nonlinear MPC problem of get_mpcInput_nonlinear (Kmpc.m:906-1181) on the device, one SQP per step."""
+
+    def __init__(self, ctx: Context, basis: Basis, Kf, Np, proj, q_run, q_term, r, lo=None, hi=None, slope_lim=None,
+                 smooth_lim=None):
+        self.ctx = ctx
+        ctx._children.add(self)
+        self.basis = basis                                   # the controller evaluates this dictionary: keep it alive
+        Kf = F.fcol(Kf); proj = F.fcol(np.atleast_2d(proj))
+        if Kf.shape != (basis.nzeta, basis.N):
+            raise ValueError(f"Kf must be nzeta x N = {basis.nzeta} x {basis.N}, it is {Kf.shape[0]} x {Kf.shape[1]}")
+        if proj.shape[1] != basis.nzeta:
+            raise ValueError(f"proj must have nzeta = {basis.nzeta} columns, it has {proj.shape[1]}")
+        self.nzeta, self.m, self.Np, self.nproj = Kf.shape[0], basis.m, int(Np), proj.shape[0]
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(r, dtype=np.float64).ravel(), (self.m,)))
+        lo_ = None if lo is None else np.ascontiguousarray(lo, dtype=np.float64)
+        hi_ = None if hi is None else np.ascontiguousarray(hi, dtype=np.float64)
+        if (lo_ is not None and lo_.size != self.m) or (hi_ is not None and hi_.size != self.m):
+            raise ValueError(f"lo and hi must have m = {self.m} entries")
+        nan = float("nan")
+        self._h = F.vp()
+        F.check(F.lib().kp_nmpc_create(ctx.handle, basis.handle, F.dptr(Kf), self.Np, F.dptr(proj), self.nproj, float(q_run),
+                                       float(q_term), F.dptr(r), F.dptr(lo_), F.dptr(hi_),
+                                       nan if slope_lim is None else float(slope_lim),
+                                       nan if smooth_lim is None else float(smooth_lim), C.byref(self._h)), ctx.handle)
+        nv, nr = C.c_int(), C.c_int()
+        F.check(F.lib().kp_nmpc_dims(self._h, C.byref(nv), C.byref(nr)))
+        self.nvar, self.nrows = nv.value, nr.value
+
+    @property
+    def handle(self):
+        return self._h
+
+    def set_state_bounds(self, lo, hi):
+        """Scaled-down bounds on every state z_0 .. z_Np (Kmpc.m:1036-1052); lo = None removes them."""
+        if lo is None:
+            F.check(F.lib().kp_nmpc_set_state_bounds(self._h, 0, None, None), self.ctx.handle)
+        else:
+            lo_ = np.ascontiguousarray(lo, dtype=np.float64); hi_ = np.ascontiguousarray(hi, dtype=np.float64)
+            if lo_.size != hi_.size:
+                raise ValueError("lo and hi must have the same length")
+            F.check(F.lib().kp_nmpc_set_state_bounds(self._h, len(lo_), F.dptr(lo_), F.dptr(hi_)), self.ctx.handle)
+        F.check(F.lib().kp_nmpc_dims(self._h, None, C.byref(nr := C.c_int())))
+        self.nrows = nr.value
+
+    def set_options(self, max_iter=60, tol_kkt=1e-8, tol_step=1e-8, damping=10.0):
+        """SQP iteration cap, stopping tolerances (KKT residual, step) and initial Levenberg-Marquardt damping."""
+        F.check(F.lib().kp_nmpc_set_options(self._h, int(max_iter), float(tol_kkt), float(tol_step), float(damping)),
+                self.ctx.handle)
+
+    def step(self, zeta, u_prev, Yr, U_init=None):
+        """Returns (U [Np x m], Z [(Np+1) x nzeta], info (iterations, KKT residual), status).  U is NaN when a QP
+        subproblem failed; status KP_ERR_NOT_CONVERGED returns the last iterate."""
+        z = np.ascontiguousarray(zeta, dtype=np.float64); up = np.ascontiguousarray(u_prev, dtype=np.float64)
+        yr = np.ascontiguousarray(Yr, dtype=np.float64)
+        ui = None if U_init is None else F.fcol(np.asarray(U_init, dtype=np.float64).reshape(self.Np, self.m))
+        U = np.zeros((self.Np, self.m), order="F"); Z = np.zeros((self.Np + 1, self.nzeta)); info = np.zeros(2)
+        st = C.c_int()
+        F.check(F.lib().kp_nmpc_step(self._h, F.dptr(z), F.dptr(up), F.dptr(yr), F.dptr(ui), F.dptr(U), F.dptr(Z), F.dptr(info),
+                                     C.byref(st)), self.ctx.handle)
+        return U, Z, info, st.value
+
+    def step_batch(self, zeta, u_prev, Yr, U_init=None):
+        """zeta (nb, nzeta), u_prev (nb, m), Yr (nb, nproj (Np+1)), U_init (nb, Np, m) or None -> U (nb, Np, m),
+        Z (nb, Np+1, nzeta), info (nb, 2), status (nb,)."""
+        z = np.ascontiguousarray(zeta, dtype=np.float64); up = np.ascontiguousarray(u_prev, dtype=np.float64)
+        yr = np.ascontiguousarray(Yr, dtype=np.float64)
+        nb = z.shape[0]
+        ui = None if U_init is None else np.ascontiguousarray(np.transpose(np.asarray(U_init, dtype=np.float64), (0, 2, 1)))
+        U = np.zeros((nb, self.m, self.Np)); Z = np.zeros((nb, self.Np + 1, self.nzeta)); info = np.zeros((nb, 2))
+        st = np.zeros(nb, dtype=np.int32)
+        F.check(F.lib().kp_nmpc_step_batch(self._h, nb, F.dptr(z), F.dptr(up), F.dptr(yr), F.dptr(ui), F.dptr(U), F.dptr(Z),
+                                           F.dptr(info), st.ctypes.data_as(F.c_ip)), self.ctx.handle)
+        return np.transpose(U, (0, 2, 1)), Z, info, st
+
+    def last_jacobians(self):
+        """[A_k B_k] = dF/d[zeta; u] at the Np points of the last linearisation of the last single step: (Np, nzeta, nvars)."""
+        nv = self.nzeta + self.m
+        J = np.zeros((self.Np, nv, self.nzeta))
+        F.check(F.lib().kp_nmpc_last_jacobians(self._h, F.dptr(J)), self.ctx.handle)
+        return np.transpose(J, (0, 2, 1))
+
+    def close(self):
+        if self._h:
+            F.lib().kp_nmpc_destroy(self._h)
             self._h = F.vp()
 
     def __del__(self):

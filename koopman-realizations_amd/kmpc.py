@@ -9,7 +9,9 @@ assemble the regression on the host and solve the constrained least squares with
 get_mpcInput_loaded does the estimate, the loaded lift and the step in one launch (kp_mpc_step_loaded); a loaded Ksim
 uses it when fused_load_step is true (the default) and the host-assembled estimate + step otherwise.
 state_bounds (Kmpc.m:300-318) are scaled down like the reference does and handed to kp_mpc_set_state_bounds.
-Out of scope: mpc_type 'nonlinear' (fmincon SQP).
+Nonlinear models (model_type 'nonlinear', mpc_type 'nonlinear'): get_mpcInput_nonlinear (Kmpc.m:1114-1181) solves the
+reference's fmincon SQP problem by a single-shooting SQP in one kernel launch (kp_nmpc_step), in the one configuration the
+reference runs: unloaded, nd = 0.  Out of scope: bilinear models with mpc_type 'nonlinear', the unused nlmpc glue.
 """
 from __future__ import annotations
 
@@ -17,7 +19,7 @@ import time
 
 import numpy as np
 
-from .device import Mpc
+from .device import Mpc, Nmpc
 
 
 class Kmpc:
@@ -46,6 +48,10 @@ class Kmpc:
         self.load_obs_horizon = 10                  # :66-67 (loaded models: past samples of the load observer's window)
         self.load_obs_period = 1                    # (steps between load estimates)
         self.fused_load_step = True                 # Ksim: estimate + lift + step in one launch (get_mpcInput_loaded)
+        self.nmpc_max_iter = 60                     # nonlinear MPC: SQP iteration cap of one step (measured counts)
+        self.nmpc_tol = 1e-8                        #   tolerance of its stopping test (KKT residual and step)
+        self.nmpc_damping = 10.0                    #   initial Levenberg-Marquardt damping of its QP Hessian
+        self.nmpc_warm_start = False                #   start from the shifted previous solution instead of the reference's X0
         self.mpc_type = "nonlinear" if self.model_type == "nonlinear" else "linear"
         for k, v in kwargs.items():                 # parse_args :107-113
             if not hasattr(self, k):
@@ -55,8 +61,19 @@ class Kmpc:
             self.input_bounds = None
         if isinstance(self.state_bounds, (list, tuple, np.ndarray)) and np.size(self.state_bounds) == 0:
             self.state_bounds = None
-        if self.mpc_type != "linear" or self.model_type == "nonlinear":
-            raise NotImplementedError("nonlinear MPC (fmincon SQP) is out of scope (SURVEY section 8)")
+        if self.mpc_type == "nonlinear" and self.model_type != "nonlinear":
+            raise NotImplementedError(f"mpc_type 'nonlinear' with a {self.model_type} model: the reference's get_BLmodel defines no "
+                                      "F_sym (Ksysid.m:1248-1278), which get_constraintMatrices_nonlinear needs (Kmpc.m:1054-1057)")
+        if self.model_type == "nonlinear":
+            if self.mpc_type != "nonlinear":
+                raise NotImplementedError("a nonlinear model has no linear MPC: get_costMatrices needs the model's A and B "
+                                          "(Kmpc.m:160-200), get_NLmodel defines only F (Ksysid.m:1298-1341)")
+            if self.loaded:
+                raise NotImplementedError("nonlinear MPC of a loaded model: nonlcon_nmpc calls F_func(z, u) with two arguments "
+                                          "(Kmpc.m:1091), the loaded model's F takes the load as a third")
+            if int(self.params.get("nd", 0)) > 0:
+                raise NotImplementedError("nonlinear MPC with delays (nd > 0): nonlcon_nmpc indexes the states by n "
+                                          "(Kmpc.m:1087-1091) while F returns nzeta = n (nd + 1) entries")
         self.projmtx = np.atleast_2d(np.asarray(self.projmtx, dtype=np.float64))
         self.expand_props()                         # :82
         m = self.params["m"]
@@ -70,9 +87,16 @@ class Kmpc:
         slope = None if self.input_slopeConst is None else float(self.input_slopeConst) * float(np.mean(sc["u_factor"]))  # :272,684
         smooth = None if self.input_smoothConst is None else \
             self.params["Ts"] ** 2 * float(self.input_smoothConst) * float(np.mean(sc["u_factor"]))                       # :294,706
-        self.dev = Mpc(self.ctx, self.model_type, self.model["A"], self.model["B"], self.horizon, self.projmtx,
-                       self.cost_running, self.cost_terminal, r, lo, hi, slope, smooth)
-        if self.state_bounds is not None:                                   # :313 state_bounds_sc = scaledown.y(state_bounds')'
+        self._U_last = None
+        if self.model_type == "nonlinear":                                  # get_cost/constraintMatrices_nonlinear (:909-1059)
+            n = self.params["n"]
+            self.dev = Nmpc(self.ctx, self.sysid.basis_dev, self.model["Kf"], self.horizon, self.projmtx[:, :n],
+                            self.cost_running, self.cost_terminal, r, lo, hi, slope, smooth)
+            self.dev.set_options(int(self.nmpc_max_iter), float(self.nmpc_tol), float(self.nmpc_tol), float(self.nmpc_damping))
+        else:
+            self.dev = Mpc(self.ctx, self.model_type, self.model["A"], self.model["B"], self.horizon, self.projmtx,
+                           self.cost_running, self.cost_terminal, r, lo, hi, slope, smooth)
+        if self.state_bounds is not None:                                   # :313 / :1050 state_bounds_sc = scaledown.y(state_bounds')'
             self.dev.set_state_bounds((self.state_bounds[:, 0] - sc["y_offset"]) / sc["y_factor"],
                                       (self.state_bounds[:, 1] - sc["y_offset"]) / sc["y_factor"])
 
@@ -216,6 +240,23 @@ class Kmpc:
         self.last_resnorm = rn
         return U, z, what
 
+    def get_mpcInput_nonlinear(self, traj, ref):
+        """Kmpc.m:1114-1181: one SQP on the device.  Returns (U, z): U (Np x m, row 1 = the pinned u_prev; NaN when a QP
+        subproblem failed), z = [zeta; 0] as the reference returns it (:1180).  self.last_info: (SQP iterations, KKT
+        residual, status)."""
+        if self.model_type != "nonlinear":
+            raise ValueError("get_mpcInput_nonlinear needs a nonlinear model")
+        zeta = self._zeta(traj)
+        u_prev = np.atleast_2d(traj["u"])[-1]
+        U_init = None
+        if self.nmpc_warm_start and self._U_last is not None and not np.isnan(self._U_last).any():
+            U_init = np.vstack([self._U_last[1:], self._U_last[-1:]])    # the previous solution shifted by one step
+        U, _, info, st = self.dev.step(zeta, u_prev, self._pad_ref(ref), U_init)
+        self._U_last = U
+        self.last_info = (int(info[0]), float(info[1]), st)
+        z = np.concatenate([zeta, np.zeros(self.params["N"] - len(zeta))])
+        return U, z
+
     def get_mpcInput(self, traj, ref):
         """Kmpc.m:329-387 (linear model)."""
         return self._step(traj, ref, 1)
@@ -296,7 +337,9 @@ class Ksim:
         The plant steps with the load of the sample the step starts from (results W, row k - 1 in 0-based rows).
         Result fields as in the reference (What: the scaled-up estimates, a zero first row).  comp_time: the reference's
         tic (Ksim.m:205) comes after the load estimate; the host-assembled path times the same span, the fused path's time
-        includes the estimate, which runs inside the same launch - the two paths' comp_time measure different work."""
+        includes the estimate, which runs inside the same launch - the two paths' comp_time measure different work.
+        Nonlinear controllers add results['nmpc_info']: (SQP iterations, KKT residual, status) of every step (status
+        KP_ERR_NOT_CONVERGED: the step returned its last iterate)."""
         mpc, s = self.mpc, self.mpc.sysid
         Np, nd = mpc.horizon, int(mpc.params["nd"])
         nx, nu = int(self.sys.params["nx"]), int(self.sys.params["nu"])
@@ -357,6 +400,9 @@ class Ksim:
                 t0 = time.perf_counter()                                      # :205
                 if mpc.model_type == "linear":
                     U, z = mpc.get_mpcInput(cur, refhor)
+                elif mpc.model_type == "nonlinear":                           # :214-215
+                    U, z = mpc.get_mpcInput_nonlinear(cur, refhor)
+                    res.setdefault("nmpc_info", []).append(mpc.last_info)     # (iterations, KKT residual, status) of the SQP
                 else:
                     U, z = mpc.get_mpcInput_bilinear_iter(cur, refhor, 1)     # :210
                 comp = time.perf_counter() - t0
