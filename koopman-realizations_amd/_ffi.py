@@ -137,6 +137,14 @@ NMPC_SIGNATURES = {
     "kp_nmpc_destroy": (C.c_int, [vp]),
 }
 
+# the batched load observer (include/koopman_hip_observer.h)
+OBSERVER_SIGNATURES = {
+    "kp_load_observe": (C.c_int, [vp, vp, C.c_int, c_dp, c_dp, C.c_int, C.c_int64, c_dp, c_dp, C.c_int,
+                                  C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int, c_dp,
+                                  C.c_int, c_dp, c_dp, c_ip]),
+}
+OBS_RATE, OBS_PIN_LAST = 1, 2      # flags of kp_load_observe
+
 _lib = None
 
 
@@ -148,7 +156,7 @@ def lib():
             raise OSError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(make -C koopman-realizations_amd/csrc)")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in (SIGNATURES | NMPC_SIGNATURES).items():
+        for name, (res, args) in (SIGNATURES | NMPC_SIGNATURES | OBSERVER_SIGNATURES).items():
             fn = getattr(l, name)
             fn.restype, fn.argtypes = res, args
         _lib = l

@@ -76,9 +76,10 @@ struct kp_ctx {
   double timers[12] = {0};
   double gram_flops_per_pair = 0;
   // growable device workspaces
-  void* ws[20] = {nullptr};     // slot 8: staging of the collectives, 9: rank-revealing solve, 10 / 11: Grams of the shadow dictionary of a dim_red fit, their half-transformed form
-  size_t ws_bytes[20] = {0};   // 12 / 13: column states and results of the lasso homotopy (kp_lasso_path.hip); 14: econ-lifted rows of a dim_red fit (kp_gram3.hip)
+  void* ws[21] = {nullptr};     // slot 8: staging of the collectives, 9: rank-revealing solve, 10 / 11: Grams of the shadow dictionary of a dim_red fit, their half-transformed form
+  size_t ws_bytes[21] = {0};   // 12 / 13: column states and results of the lasso homotopy (kp_lasso_path.hip); 14: econ-lifted rows of a dim_red fit (kp_gram3.hip)
                                 // 15 / 16: lifted snapshot panels of a wide dictionary, 17: split partials of its products, 18: scratch of the blocked factorisation (kp_wide.hip, kp_fit.hip)
+                                // 20: inputs, per-row blocks and results of the batched load observer (kp_observer.hip)
   int last_rank = -1;           // rank found by the most recent solve (W when the Gram matrix was positive definite)
   double last_pivot_ratio = 1.0; // min_i L_ii^2 / G_ii of the most recent synchronous least-squares solve (~1 / cond(G))
   // results of the last kp_fit

@@ -227,6 +227,32 @@ class Context:
         F.check(F.lib().kp_lift_jacobian(self._h, basis.handle, rows, F.dptr(V), F.dptr(J)), self._h)
         return np.transpose(J, (0, 2, 1))
 
+    def load_observe(self, basis, model_type, A, B, nw, trials, win_trial, win_start, hor, whatpast=None, flags=0):
+        """kp_load_observe: the load estimate of every window, one call.  basis: the unloaded dictionary; A, B: the loaded
+        model (N (nw + 1) rows); trials: a list of (zeta, u) pairs of row arrays (rows x nzeta, rows x m), already padded;
+        window w covers rows win_start[w] .. win_start[w] + hor - 1 of trial win_trial[w].  whatpast (nwin x nw) with
+        flags & OBS_RATE.  Returns (what (nwin x nw), resnorm (nwin), status (nwin)): NaN and KP_ERR_QP_FAIL for a window
+        without a unique estimate."""
+        zs = [np.asarray(z, dtype=np.float64).reshape(-1, basis.nzeta) for z, _ in trials]
+        us = [np.asarray(u, dtype=np.float64).reshape(-1, basis.m) for _, u in trials]
+        if any(z.shape[0] != u.shape[0] for z, u in zip(zs, us)):
+            raise ValueError("every trial needs as many input rows as state rows")
+        lens = [z.shape[0] for z in zs]
+        Z = F.fcol(np.vstack(zs)); U = F.fcol(np.vstack(us)); A = F.fcol(A); B = F.fcol(B)
+        off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(lens)]), dtype=np.int64)
+        wt = np.ascontiguousarray(win_trial, dtype=np.int32); ws = np.ascontiguousarray(win_start, dtype=np.int64)
+        nwin = wt.size
+        if ws.size != nwin:
+            raise ValueError("win_trial and win_start must have the same length")
+        wp = None if whatpast is None else np.ascontiguousarray(np.asarray(whatpast, dtype=np.float64).reshape(nwin, int(nw)))
+        what = np.zeros((nwin, int(nw))); res = np.zeros(nwin); st = np.zeros(nwin, dtype=np.int32)
+        F.check(F.lib().kp_load_observe(self._h, basis.handle, F.MODEL[model_type], F.dptr(A), F.dptr(B), int(nw), int(Z.shape[0]),
+                                        F.dptr(Z), F.dptr(U), len(trials), off.ctypes.data_as(C.POINTER(C.c_int64)), nwin,
+                                        wt.ctypes.data_as(C.POINTER(C.c_int32)), ws.ctypes.data_as(C.POINTER(C.c_int64)),
+                                        int(hor), F.dptr(wp), int(flags), F.dptr(what), F.dptr(res),
+                                        st.ctypes.data_as(F.c_ip)), self._h)
+        return what, res, st
+
     def qp_solve(self, H, f, A, b):
         """quadprog_gurobi(H,f,A,b) shim: NaN vector on failure (quadprog_gurobi.m:22-23)."""
         H = F.fcol(H); A = F.fcol(A)

@@ -20,6 +20,7 @@ import numpy as np
 
 from . import _ffi as F
 from .device import Basis, Context, Snapshots, fit, fit_gram, fit_refine
+from .observer import assemble_val_observer, plan_val_observer
 
 _default_ctx = None
 
@@ -729,6 +730,96 @@ class Ksysid:
         t, yreal, ureal, zetareal = self._val_common(valdata)
         zs = self.ctx.rollout_nl(self.basis_dev, model["Kf"], zetareal[0], ureal)   # one launch for the whole trial
         return self._results(t, ureal, zs[:, :self.params["n"]], yreal)
+
+    # ---- load observer (Ksysid.m:1975-2139) ------------------------------------------------------------
+    def _observer_model(self):
+        """The model the observer regresses with, after the reference's limits: loaded, linear or bilinear, nd = 0."""
+        if not self.loaded:
+            raise ValueError("the load observer needs a loaded model (loaded = true)")
+        if self.model_type == "nonlinear":
+            raise NotImplementedError("the reference has no load observer for a nonlinear loaded model")
+        if self.params["nd"] > 0:
+            raise ValueError("the load observer does not work with delays (nd > 0): Ksysid.m:1986, and "
+                             "val_observer_load would index zeta past its end")
+        if self.model is None:
+            raise ValueError("no model: call train_models first")
+        return self.model
+
+    def observer_load(self, ypast, upast, whatpast=None):
+        """Ksysid.m:1978-2030 on the device (kp_load_observe, one window): the load estimate from the hor rows of the past
+        (ypast: hor x n, upast: hor x m, scaled).  The hor - 1 pairs (zeta_k, zeta_{k+1}) with input u_k give the rows
+        C A kron(I_{nw+1}, psi(zeta_k)) [1; w] = y_{k+1} - C B u_k, psi = econ_full and C A = A[:n, :]: the lift.Omega of
+        :1995, which def_observables_loaded never defines, is read as kron(eye(nw+1), econ_full(zeta)), as
+        Kmpc.estimate_load_linear builds it (Kmpc.m:1320-1324).  For a bilinear model :2003-2008 does not fit B
+        (n x m N (nw+1)), so the rows are the reference's only bilinear observer regression, Kmpc.m:1384-1394:
+        (A[:n] + sum_j u_kj B_j[:n]) kron(I, psi(zeta_k)) [1; w] = zeta_{k+1} (an extension).  The lsqlin of :2021-2026:
+        x = [1; w], -1 <= w <= 1; whatpast adds |w - whatpast(end, :)| <= 0.01 (:2010-2019, whose A has 2 nw rows and b
+        nw + 1: read as one bound per load, as Kmpc._lsqlin_load does).  No load is pinned (that equality is Kmpc's,
+        Kmpc.m:1350).  Returns (what (nw), resnorm = ||C x - d||^2); NaN when the window does not determine the loads."""
+        model = self._observer_model()
+        ypast = np.atleast_2d(np.asarray(ypast, dtype=np.float64)); upast = np.atleast_2d(np.asarray(upast, dtype=np.float64))
+        hor = ypast.shape[0]
+        if upast.shape[0] != hor:                                          # :1987-1990
+            raise ValueError("Input arguments must have the same number of rows")
+        if hor < 2:
+            raise ValueError("observer_load needs hor >= 2 rows (one pair)")
+        _, zp = self.get_zeta({"y": ypast, "u": upast})
+        flags, wp = 0, None
+        if whatpast is not None:
+            flags, wp = F.OBS_RATE, np.atleast_2d(np.asarray(whatpast, dtype=np.float64))[-1]
+        what, res, _ = self.ctx.load_observe(self.basis_dev, self.model_type, model["A"], model["B"], self.params["nw"],
+                                             [(zp, upast)], [0], [0], hor, wp, flags)
+        return what[0], float(res[0])
+
+    def _val_observer(self, hor, update_hor, valdata):
+        model = self._observer_model()
+        if int(hor) != hor or hor < 2:
+            raise ValueError("hor must be an integer >= 2")
+        if update_hor is not None and (int(update_hor) != update_hor or update_hor < 1):
+            raise ValueError("update_hor must be an integer >= 1")
+        hor = int(hor)
+        single = isinstance(valdata, dict)
+        runs = [valdata] if single else list(valdata)
+        nw = self.params["nw"]
+        trials, plans, wreal, win_trial, win_start = [], [], [], [], []
+        for q, v in enumerate(runs):
+            T = len(np.ravel(v["t"]))
+            y = np.atleast_2d(np.asarray(v["y"], dtype=np.float64)); u = np.asarray(v["u"], dtype=np.float64)
+            w = np.asarray(v["w"], dtype=np.float64)
+            if y.shape[0] != T or u.reshape(len(u), -1).shape[0] != T or w.reshape(len(w), -1).shape[0] != T:
+                raise ValueError(f"valdata {q}: t, y, u and w must have the same number of rows")
+            _, zeta = self.get_zeta(v)
+            zpad, upad, steps = plan_val_observer(zeta, u.reshape(T, -1), hor, update_hor)
+            trials.append((zpad, upad)); plans.append((T, steps)); wreal.append(w.reshape(T, nw))
+            win_trial.append(np.full(len(steps), q)); win_start.append(steps - 1)
+        est, res, _ = self.ctx.load_observe(self.basis_dev, self.model_type, model["A"], model["B"], nw, trials,
+                                            np.concatenate(win_trial), np.concatenate(win_start), hor)
+        outs, k = [], 0
+        for (T, steps), wr in zip(plans, wreal):
+            e, r = est[k:k + len(steps)], res[k:k + len(steps)]
+            k += len(steps)
+            if update_hor is None:
+                what = assemble_val_observer(T, nw, steps, e)
+                outs.append((what, wr, np.abs(wr - what)))
+            else:
+                what, rs = assemble_val_observer(T, nw, steps, e, r, sparse=True)
+                outs.append((what, wr, np.abs(wr - what), rs))
+        return outs[0] if single else tuple(list(c) for c in zip(*outs))
+
+    def val_observer_load(self, hor, valdata):
+        """Ksysid.m:2033-2075: the observer's estimate at every step of a validation trial (scaled, as ks.valdata), all
+        windows in one device call.  what (T x nw): what(1) = 0, what(i+1) the estimate from zeta(i-hor+1 .. i) and
+        u(i-hor+1 .. i), rows before sample 1 zero (the zero history of :2046-2047, lifted like any state); the windows
+        as observer_load without whatpast (:2061).  Returns (what, wreal = valdata.w, werr = |wreal - what|).  A list of
+        trials is one device call and returns a tuple of lists."""
+        return self._val_observer(hor, None, valdata)
+
+    def val_observer_load_sparse(self, hor, update_hor, valdata):
+        """Ksysid.m:2079-2139: as val_observer_load, but the input history takes u(i+1) at step i (:2106 - a one-step
+        shift of the reference, reproduced) and an estimate is made only when mod(i, update_hor) == 0; what(i+1) is then
+        the mean of all estimates so far and res(i+1) = resnorm + 1e-6, else both hold their previous values; res(1) =
+        1e-6.  Returns (what, wreal, werr, res); a list of trials returns a tuple of lists."""
+        return self._val_observer(hor, update_hor, valdata)
 
     def get_error(self, simdata, realdata):
         """Ksysid.m:1882-1898.  Diverged rollouts give Inf / NaN errors silently, as MATLAB does."""
