@@ -1,6 +1,7 @@
 """Command line: identify a Koopman model from a reference data file, without MATLAB.
 
-    python -m koopman_realizations_amd sysid DATA.mat --model_type bilinear --obs_degree 3 [--dim_red] [--out model.npz]
+    python -m koopman_realizations_amd sysid DATA.mat --model_type bilinear --obs_degree 3 [--dim_red]
+        [--time_type continuous] [--out model.npz]
 
 is example_sysid.m:22-65 (Ksysid constructor, train_models, validation of every `val` trial) with the options of
 Ksysid_setup.m; prints the validation errors and optionally stores the model matrices."""
@@ -25,6 +26,7 @@ def main(argv=None):
     s.add_argument("--delays", type=int, default=0)
     s.add_argument("--dim_red", action="store_true")
     s.add_argument("--loaded", action="store_true")
+    s.add_argument("--time_type", default="discrete", choices=["discrete", "continuous"])
     s.add_argument("--device", type=int, default=0)
     s.add_argument("--out", default=None, help="write the model (A, B, C, K, scale) to this .npz")
     a = ap.parse_args(argv)
@@ -34,11 +36,12 @@ def main(argv=None):
     data = load_data4sysid(a.data)
     ctx = Context(a.device)
     ks = Ksysid(data, ctx=ctx, model_type=a.model_type, obs_type=a.obs_type, obs_degree=a.obs_degree, snapshots=a.snapshots,
-                lasso=a.lasso if len(a.lasso) > 1 else a.lasso[0], delays=a.delays, dim_red=a.dim_red, loaded=a.loaded)
+                lasso=a.lasso if len(a.lasso) > 1 else a.lasso[0], delays=a.delays, dim_red=a.dim_red, loaded=a.loaded,
+                time_type=a.time_type)
     ks.train_models()
     val = {"linear": ks.val_model, "bilinear": ks.val_BLmodel, "nonlinear": ks.val_NLmodel}[a.model_type]
     p = ks.params
-    print(f"{a.model_type} model: n={p['n']} m={p['m']} nzeta={p['nzeta']} N={p['N']}  pairs={len(ks.snapshotPairs['alpha'])}")
+    print(f"{a.model_type} {a.time_type}-time model: n={p['n']} m={p['m']} nzeta={p['nzeta']} N={p['N']}  pairs={len(ks.snapshotPairs['alpha'])}")
     for i, v in enumerate(ks.valdata):
         e = val(ks.model, v)["error"]
         print(f"val trial {i}: rmse {np.array2string(e['rmse'], precision=4)}  nrmse {np.array2string(e['nrmse'], precision=4)}  "

@@ -29,10 +29,11 @@ _E = np.array([71 / 57600, 0, -71 / 16695, 71 / 1920, -17253 / 339200, 22 / 525,
 _C = np.array([0, 1 / 5, 3 / 10, 4 / 5, 8 / 9, 1, 1])
 
 
-def dopri45(f, t0, tf, y0, rtol=1e-3, atol=1e-6):
+def dopri45(f, t0, tf, y0, rtol=1e-3, atol=1e-6, stats=None):
     """Integrate y' = f(t, y) from t0 to tf; returns y(tf).  Step control as ode45's:
     error norm = max |e_i| / max(|y_i|, |ynew_i|, atol/rtol); shrink by max(0.1, 0.8 (rtol/err)^(1/5))
-    on the first failure of a step and by 1/2 afterwards; grow by at most 5x after a clean step."""
+    on the first failure of a step and by 1/2 afterwards; grow by at most 5x after a clean step.
+    stats: a dict whose "naccept" / "nreject" entries are incremented by the steps taken."""
     y = np.asarray(y0, dtype=np.float64).copy()
     t = float(t0)
     span = tf - t0
@@ -63,6 +64,8 @@ def dopri45(f, t0, tf, y0, rtol=1e-3, atol=1e-6):
             if err > rtol:
                 if h <= hmin:
                     raise RuntimeError("dopri45: step size underflow")
+                if stats is not None:
+                    stats["nreject"] = stats.get("nreject", 0) + 1
                 if nofail:
                     nofail = False
                     h = max(hmin, h * max(0.1, 0.8 * (rtol / err) ** 0.2))
@@ -76,6 +79,8 @@ def dopri45(f, t0, tf, y0, rtol=1e-3, atol=1e-6):
         else:
             hnext = h
         t, y = tnew, ynew
+        if stats is not None:
+            stats["naccept"] = stats.get("naccept", 0) + 1
         k[0] = k[6]
         h = hnext
     return y

@@ -218,6 +218,66 @@ class Context:
         F.check(F.lib().kp_rollout_nl(self._h, basis.handle, 1, F.dptr(Kf), F.dptr(z0), F.dptr(U), T, F.dptr(Z)), self._h)
         return Z
 
+    def logm(self, A, shift=0.0, scale=1.0):
+        """kp_logm: scale * logm(A_b + shift I) of one n x n matrix or a stack (nb, n, n).  Returns (L, nsqrt, status):
+        L NaN and status KP_ERR_NOT_CONVERGED for a matrix without a reachable real principal logarithm."""
+        A = np.asarray(A, dtype=np.float64)
+        single = A.ndim == 2
+        if single:
+            A = A[None]
+        nb, n = A.shape[0], A.shape[1]
+        if A.shape[2] != n:
+            raise ValueError("kp_logm: square matrices only")
+        Ac = np.ascontiguousarray(np.transpose(A, (0, 2, 1)))        # each matrix column-major
+        L = np.zeros_like(Ac)
+        nsq = np.zeros(nb, dtype=np.int32); st = np.zeros(nb, dtype=np.int32)
+        F.check(F.lib().kp_logm(self._h, nb, n, F.dptr(Ac), float(shift), float(scale), F.dptr(L),
+                                nsq.ctypes.data_as(F.c_ip), st.ctypes.data_as(F.c_ip)), self._h)
+        L = np.transpose(L, (0, 2, 1))
+        return (L[0], int(nsq[0]), int(st[0])) if single else (L, nsq, st)
+
+    def rollout_ct(self, model_type, A, B, z0, U, n_out, Ts, rtol=1e-3, atol=1e-6):
+        """kp_rollout_ct: ode45 over every sample interval of z' = A z + B u (linear) or A z + sum_i u_i B_i z (bilinear),
+        batched like `rollout`.  Returns (Y, naccept, nreject, status); a rollout that failed is NaN from the failing
+        sample on, with status KP_ERR_NOT_CONVERGED."""
+        A = np.asarray(A, dtype=np.float64); B = np.asarray(B, dtype=np.float64)
+        z0 = np.asarray(z0, dtype=np.float64); U = np.asarray(U, dtype=np.float64)
+        single = A.ndim == 2
+        if single:
+            A, B, z0, U = A[None], B[None], z0[None], U[None]
+        batch, N = A.shape[0], A.shape[1]
+        T, m = U.shape[1], U.shape[2]
+        Ac = np.ascontiguousarray(np.transpose(A, (0, 2, 1)))
+        Bc = np.ascontiguousarray(np.transpose(B, (0, 2, 1)))
+        Uc = np.ascontiguousarray(np.transpose(U, (0, 2, 1)))
+        Y = np.zeros((batch, n_out, T))
+        na = np.zeros(batch, dtype=np.int32); nr = np.zeros(batch, dtype=np.int32); st = np.zeros(batch, dtype=np.int32)
+        F.check(F.lib().kp_rollout_ct(self._h, F.MODEL[model_type], batch, F.dptr(Ac), F.dptr(Bc), N, m,
+                                      F.dptr(np.ascontiguousarray(z0)), F.dptr(Uc), T, n_out, float(Ts), float(rtol), float(atol),
+                                      F.dptr(Y), na.ctypes.data_as(F.c_ip), nr.ctypes.data_as(F.c_ip), st.ctypes.data_as(F.c_ip)),
+                self._h)
+        Y = np.transpose(Y, (0, 2, 1))
+        return (Y[0], int(na[0]), int(nr[0]), int(st[0])) if single else (Y, na, nr, st)
+
+    def rollout_nl_ct(self, basis, Kf, zeta0, U, Ts, rtol=1e-3, atol=1e-6):
+        """kp_rollout_nl_ct: ode45 over every sample interval of zeta' = Kf econ_full([zeta; u]).  Kf (nzeta, N) or
+        (nb, nzeta, N), zeta0 (nzeta,) / (nb, nzeta), U (T, m) / (nb, T, m).  Returns (Z, naccept, nreject, status)."""
+        Kf = np.asarray(Kf, dtype=np.float64); z0 = np.asarray(zeta0, dtype=np.float64); U = np.asarray(U, dtype=np.float64)
+        single = Kf.ndim == 2
+        if single:
+            Kf, z0, U = Kf[None], z0[None], np.atleast_2d(U)[None]
+        nb, nz, N = Kf.shape
+        T = U.shape[1]
+        Kc = np.ascontiguousarray(np.transpose(Kf, (0, 2, 1)))
+        Uc = np.ascontiguousarray(np.transpose(U, (0, 2, 1)))
+        Z = np.zeros((nb, nz, T))
+        na = np.zeros(nb, dtype=np.int32); nr = np.zeros(nb, dtype=np.int32); st = np.zeros(nb, dtype=np.int32)
+        F.check(F.lib().kp_rollout_nl_ct(self._h, basis.handle, nb, F.dptr(Kc), F.dptr(np.ascontiguousarray(z0)), F.dptr(Uc), T,
+                                         float(Ts), float(rtol), float(atol), F.dptr(Z), na.ctypes.data_as(F.c_ip),
+                                         nr.ctypes.data_as(F.c_ip), st.ctypes.data_as(F.c_ip)), self._h)
+        Z = np.transpose(Z, (0, 2, 1))
+        return (Z[0], int(na[0]), int(nr[0]), int(st[0])) if single else (Z, na, nr, st)
+
     def lift_jacobian(self, basis, V):
         """kp_lift_jacobian: d econ_full / dv at the rows of V (rows x nvars; v = [zeta, u] for a nonlinear dictionary)
         -> (rows, N, nvars)."""

@@ -27,6 +27,8 @@ class Kmpc:
 
     def __init__(self, sysid_class, **kwargs):
         s = sysid_class
+        if getattr(s, "time_type", "discrete") == "continuous":     # Kmpc.m never reads time_type: it would build a wrong controller
+            raise ValueError("Kmpc needs a discrete-time model: this Ksysid has time_type='continuous'")
         self.sysid = s
         self.ctx = s.ctx
         self.params = s.params                      # Kmpc.m:44

@@ -10,7 +10,12 @@ scaling bookkeeping, snapshot selection, dictionary description.
 loaded=True (Ksysid.m:539-626: lifted state [1; w] (x) psi for a load vector w) is expressed with the same device
 kernels: [1; u] (x) [1; w] (x) psi is the bilinear row of psi for a pseudo-input built from u and w, so any dictionary
 (every obs_type, with or without dim_red) goes through the Kronecker Gram kernels unchanged (`_def_observables_loaded`).
-Not supported (KP scope): time_type='continuous'.
+
+time_type='continuous' (Ksysid.m:1186-1187, 1245-1246, 1307-1310): the model is (1/Ts) logm(K + 1e-12 I) of the fitted K,
+computed on the device (kp_logm; a lasso grid is one batched call), and validation integrates every sample interval with
+ode45's Dormand-Prince pair and step control on the device (kp_rollout_ct / kp_rollout_nl_ct, RelTol 1e-3, AbsTol 1e-6).
+A K without a real principal logarithm (a negative eigenvalue) is refused, where MATLAB returns a complex model.  Loaded
+continuous models are not supported: the reference's loaded validation ignores time_type.
 """
 from __future__ import annotations
 
@@ -176,6 +181,7 @@ class Ksysid:
         self.snapshots = math.inf; self.lasso = 1e6; self.delays = 0
         self.model_type = "linear"; self.loaded = False; self.time_type = "discrete"; self.dim_red = False
         self.ls_refine = 1     # (not a reference property) refinement steps after the normal-equations solve: `\` is a QR solve
+        self.ode_rtol, self.ode_atol = 1e-3, 1e-6    # (not reference properties) the ode45 tolerances of continuous-time validation
         self._host_only = bool(kwargs.pop("_host_only", False))           # sweeps: scaling / pairs only, no device dictionary
         self._pca_host = bool(kwargs.pop("_pca_host", False))             # cross-check: pca by host SVD of the lifted matrix
         for k, v in kwargs.items():                                        # parse_args :147-158
@@ -187,8 +193,11 @@ class Ksysid:
         self.lasso = las if las.size > 1 else float(las[0])
         if self.loaded and "w" not in data:                                # :106-109
             raise ValueError("You have specified a loaded system, but your training data does not have the required load field (w)")
-        if self.time_type != "discrete":
-            raise NotImplementedError("continuous-time models are out of scope (SURVEY section 8)")
+        if self.time_type not in ("discrete", "continuous"):
+            raise ValueError("time_type must be 'discrete' or 'continuous'")
+        if self.time_type == "continuous" and self.loaded:
+            raise NotImplementedError("loaded continuous-time models are not supported: the reference validates them with the "
+                                      "discrete recursion (Ksysid.m:1657-1671)")
         if self.model_type not in ("linear", "bilinear", "nonlinear"):    # :96-104
             raise ValueError("Invalid model_type chosen. Must be linear, bilinear, or nonlinear.")
         self.liftinput = {"linear": 0, "nonlinear": 1, "bilinear": 2}[self.model_type]
@@ -585,10 +594,31 @@ class Ksysid:
         K[:, free] = self.ctx.fit_lasso(G, np.asfortranarray(C[:, free]), t - len(ones))[0]
         return K
 
-    def get_model(self, koopData):
-        """Ksysid.m:1179-1235 (discrete): A, B, C and the projection M."""
+    # ---- continuous time -------------------------------------------------------------------
+    def _logm_K(self, Ks):
+        """(1/Ts) logm(K + 1e-12 I) of one K or a list of them (one batched device call).  logm(K') = logm(K)', so the UT of
+        get_model / get_BLmodel (:1186, :1245) is the transpose of this and get_NLmodel's K (:1309) is this."""
+        single = not isinstance(Ks, (list, tuple))
+        stack = np.stack([np.asarray(k, dtype=np.float64) for k in ([Ks] if single else Ks)])
+        L, _, status = self.ctx.logm(stack, 1e-12, 1.0 / self.params["Ts"])
+        bad = [i for i, st in enumerate(status) if st != F.KP_OK]
+        if bad:
+            raise F.KoopmanHipError(F.KP_ERR_NOT_CONVERGED, f"logm(K + 1e-12 I): no real principal logarithm for candidate(s) {bad} "
+                                    "(K has a negative eigenvalue; the reference would return a complex model)")
+        return L[0] if single else list(L)
+
+    def _Kc(self, koopData, Kc):
+        if self.time_type != "continuous":
+            return None
+        return self._logm_K(koopData["K"]) if Kc is None else Kc
+
+    def get_model(self, koopData, Kc=None):
+        """Ksysid.m:1179-1235: A, B, C and the projection M.  Continuous time: A, B are the blocks of
+        (1/Ts) logm(K' + 1e-12 I), not projected; M is still computed from them (:1206-1222).  Kc: that logarithm (untransposed)
+        when the caller already has it."""
         p = self.params; N, n, m = p["N"], p["n"], p["m"]
         K = koopData["K"]
+        Kc = self._Kc(koopData, Kc)
         if self.loaded:                                                    # :1192-1200: every size is N (nw + 1)
             N = N * (p["nw"] + 1)
             snaps, _ = self._loaded_snapshots(koopData)
@@ -602,25 +632,33 @@ class Ksysid:
                 G, Cm = fit_gram(self.ctx, self.basis_dev, snaps)
             finally:
                 snaps.close()
-        A, B, M = self.ctx.model_project(K, G, Cm, N, m)
+        if Kc is None:
+            A, B, M = self.ctx.model_project(K, G, Cm, N, m)
+        else:
+            _, _, M = self.ctx.model_project(Kc, G, Cm, N, m)
+            A = np.asfortranarray(Kc[:N, :N].T); B = np.asfortranarray(Kc[N:, :N].T)
         out = {"A": A, "B": B, "C": np.hstack([np.eye(n), np.zeros((n, N - n))]), "M": M, "params": dict(p), "K": K}
         self.model = out
         return out
 
-    def get_BLmodel(self, koopData):
-        """Ksysid.m:1238-1282 (with loads every size is N (nw + 1), :1251-1259)."""
+    def get_BLmodel(self, koopData, Kc=None):
+        """Ksysid.m:1238-1282 (with loads every size is N (nw + 1), :1251-1259); continuous time: the blocks of
+        (1/Ts) logm(K' + 1e-12 I)."""
         p = self.params; N, n, m = p["N"] * (p["nw"] + 1), p["n"], p["m"]
-        UT = koopData["K"].T
+        Kc = self._Kc(koopData, Kc)
+        UT = (koopData["K"] if Kc is None else Kc).T
         A = np.asfortranarray(UT[:N, :N]); B = np.asfortranarray(UT[:N, N:])
         out = {"A": A, "B": B, "C": np.hstack([np.eye(n), np.zeros((n, N - n))]), "params": dict(p), "K": koopData["K"],
                "Beta": lambda z: np.stack([B[:, i * N:(i + 1) * N] @ np.ravel(z) for i in range(m)], axis=1)}
         self.model = out
         return out
 
-    def get_NLmodel(self, koopData):
-        """Ksysid.m:1298-1341: F(zeta,u) = K(:,1:nzeta)' * basis([zeta;u])."""
+    def get_NLmodel(self, koopData, Kc=None):
+        """Ksysid.m:1298-1341: F(zeta,u) = K(:,1:nzeta)' * basis([zeta;u]); continuous time (:1307-1310) with
+        K = (1/Ts) logm(K + 1e-12 I), F is then the vector field zeta' = F(zeta, u)."""
         p = self.params
-        Kf = np.ascontiguousarray(koopData["K"][:, :p["nzeta"]].T)
+        Kc = self._Kc(koopData, Kc)
+        Kf = np.ascontiguousarray((koopData["K"] if Kc is None else Kc)[:, :p["nzeta"]].T)
         if self.loaded:                                                    # :1320-1327
             ff = lambda zeta, u, w: Kf @ self.lift.econ_full_loaded(np.concatenate([np.ravel(zeta), np.ravel(u)]), np.ravel(w))
         else:
@@ -647,7 +685,10 @@ class Ksysid:
                 kd = self.get_Koopman(self.snapshotPairs, float(lv))
                 kd["beta"] = self.snapshotPairs["beta"]
                 self.koopData.append(kd)
-                c = extract(kd); c["lasso"] = float(lv)
+            # continuous time: the logarithms of every candidate in one batched device call
+            Kcs = self._logm_K([kd["K"] for kd in self.koopData]) if self.time_type == "continuous" else [None] * len(las)
+            for kd, lv, Kc in zip(self.koopData, las, Kcs):
+                c = extract(kd, Kc); c["lasso"] = float(lv)
                 self.candidates.append(c)
             self.model = self.candidates[0]
         return self
@@ -703,13 +744,19 @@ class Ksysid:
         res["sim"]["w"] = res["real"]["w"] = wreal                             # :1707-1710
         return res
 
+    def _rollout(self, kind, model, z0, ureal):
+        if self.time_type == "continuous":                                 # :1679-1683, :1777-1781: ode45 per sample
+            return self.ctx.rollout_ct(kind, model["A"], model["B"], z0, ureal, self.params["n"], self.params["Ts"],
+                                       self.ode_rtol, self.ode_atol)[0]
+        return self.ctx.rollout(kind, model["A"], model["B"], z0, ureal, self.params["n"])
+
     def val_model(self, model, valdata):
-        """Ksysid.m:1623-1714: z+ = A z + B u rolled out on the device."""
+        """Ksysid.m:1623-1714: z+ = A z + B u (continuous time: z' = A z + B u) rolled out on the device."""
         if self.loaded:
             return self._val_loaded(model, valdata, "linear")
         t, yreal, ureal, zetareal = self._val_common(valdata)
         z0 = self.lift.econ_full(zetareal[0])
-        Y = self.ctx.rollout("linear", model["A"], model["B"], z0, ureal, self.params["n"])
+        Y = self._rollout("linear", model, z0, ureal)
         Y[0] = yreal[0]                                                    # :1654
         return self._results(t, ureal, Y, yreal)
 
@@ -719,7 +766,7 @@ class Ksysid:
             return self._val_loaded(model, valdata, "bilinear")
         t, yreal, ureal, zetareal = self._val_common(valdata)
         z0 = self.lift.econ_full(zetareal[0])
-        Y = self.ctx.rollout("bilinear", model["A"], model["B"], z0, ureal, self.params["n"])
+        Y = self._rollout("bilinear", model, z0, ureal)
         Y[0] = yreal[0]
         return self._results(t, ureal, Y, yreal)
 
@@ -728,7 +775,11 @@ class Ksysid:
         if self.loaded:
             return self._val_loaded(model, valdata, "nonlinear")
         t, yreal, ureal, zetareal = self._val_common(valdata)
-        zs = self.ctx.rollout_nl(self.basis_dev, model["Kf"], zetareal[0], ureal)   # one launch for the whole trial
+        if self.time_type == "continuous":                                 # :1849-1856: ode45 per sample
+            zs = self.ctx.rollout_nl_ct(self.basis_dev, model["Kf"], zetareal[0], ureal, self.params["Ts"],
+                                           self.ode_rtol, self.ode_atol)[0]
+        else:
+            zs = self.ctx.rollout_nl(self.basis_dev, model["Kf"], zetareal[0], ureal)   # one launch for the whole trial
         return self._results(t, ureal, zs[:, :self.params["n"]], yreal)
 
     # ---- load observer (Ksysid.m:1975-2139) ------------------------------------------------------------
