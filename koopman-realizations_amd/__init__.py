@@ -13,8 +13,9 @@ from .device import Mpc, Nmpc
 from . import comm
 from .multi import Multi, MultiMpc
 from .arm import Arm
+from .arm_device import DeviceArm
 from .kmpc import Kmpc, Ksim, ModelPlant
 from .ksysid import Ksysid, default_context, poly_exponent_table
 
-__all__ = ["Arm", "Basis", "Context", "Snapshots", "fit", "fit_gram", "fit_gram_sharded", "fit_refine", "fit_sharded", "Ksysid", "Kmpc", "Ksim", "ModelPlant", "Mpc", "KoopmanHipError", "default_context",
+__all__ = ["Arm", "DeviceArm", "Basis", "Context", "Snapshots", "fit", "fit_gram", "fit_gram_sharded", "fit_refine", "fit_sharded", "Ksysid", "Kmpc", "Ksim", "ModelPlant", "Mpc", "KoopmanHipError", "default_context",
            "poly_exponent_table", "_ffi", "comm", "Multi", "MultiMpc"]

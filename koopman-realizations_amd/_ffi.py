@@ -154,6 +154,18 @@ CT_SIGNATURES = {
                                    c_ip]),
 }
 
+# the arm plant (include/koopman_hip_arm.h)
+class KpArmParams(C.Structure):
+    _fields_ = [("Nmods", C.c_int), ("nlinks", C.c_int), ("l", C.c_double), ("k", C.c_double), ("d", C.c_double),
+                ("m", C.c_double), ("i", C.c_double), ("g", C.c_double), ("ku", C.c_double)]
+
+
+ARM_SIGNATURES = {
+    "kp_arm_simulate": (C.c_int, [vp, C.POINTER(KpArmParams), C.c_int, C.c_int, C.c_int, c_dp, C.c_double, c_dp, c_dp, c_dp,
+                                  C.c_double, C.c_double, c_dp, c_ip, c_ip, c_ip]),
+}
+ARM_MODE = {"zoh": 0, "interp": 1, "floor": 2, "restart": 3}      # KP_ARM_SPAN_ZOH, _SPAN_INTERP, _SPAN_FLOOR, KP_ARM_RESTART
+
 _lib = None
 
 
@@ -165,7 +177,7 @@ def lib():
             raise OSError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(make -C koopman-realizations_amd/csrc)")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in (SIGNATURES | NMPC_SIGNATURES | OBSERVER_SIGNATURES | CT_SIGNATURES).items():
+        for name, (res, args) in (SIGNATURES | NMPC_SIGNATURES | OBSERVER_SIGNATURES | CT_SIGNATURES | ARM_SIGNATURES).items():
             fn = getattr(l, name)
             fn.restype, fn.argtypes = res, args
         _lib = l

@@ -225,3 +225,84 @@ class Arm:
             X[k + 1] = self.simulate_Ts(X[k], u_in[k], w_in[k], t_in[k + 1] - t_in[k])
         return {"t": t_in, "x": X, "alpha": X[:, :n], "alphadot": X[:, n:], "y": self.get_y(X), "u": u_in,
                 "w": np.array(w_in), "params": self.params}
+
+
+# ntrp45's interpolation matrix: y(t + s h) = y + h K BI [s s^2 s^3 s^4]^T, K the 7 stages of the step
+_BI = np.array([
+    [1, -183 / 64, 37 / 12, -145 / 128],
+    [0, 0, 0, 0],
+    [0, 1500 / 371, -1000 / 159, 1000 / 371],
+    [0, -125 / 32, 125 / 12, -375 / 64],
+    [0, 9477 / 3392, -729 / 106, 25515 / 6784],
+    [0, -11 / 7, 11 / 3, -55 / 28],
+    [0, 3 / 2, -4, 5 / 2],
+])
+
+
+def ode45_span(f, tspan, y0, rtol=1e-3, atol=1e-6, stats=None):
+    """ode45 with a time vector (tspan of more than two points): ONE integration over [tspan[0], tspan[-1]] and the
+    solution at every tspan point, exact where a step ends on it and from ntrp45's interpolant otherwise.  Returns
+    Y (len(tspan) x n).  Step control as dopri45 (the same tableau), with ode45's MaxStep 0.1 (tf - t0) and initial
+    trial step min(MaxStep, tspan[1] - tspan[0]).  f(t, y) is called at the stage times, so a right-hand side that
+    selects an input row by t sees what ode45's sees.  stats: as dopri45."""
+    tspan = np.asarray(tspan, dtype=np.float64).ravel()
+    if tspan.size < 2 or not (np.diff(tspan) > 0).all():
+        raise ValueError("tspan must hold at least two strictly increasing times")
+    y = np.asarray(y0, dtype=np.float64).copy()
+    Y = np.empty((tspan.size, y.size))
+    Y[0] = y
+    t, tf = float(tspan[0]), float(tspan[-1])
+    thr = atol / rtol
+    hmax = 0.1 * (tf - t)
+    f0 = f(t, y)
+    h = min(hmax, tspan[1] - tspan[0])
+    rh = np.max(np.abs(f0 / np.maximum(np.abs(y), thr))) / (0.8 * rtol ** 0.2)
+    if h * rh > 1:
+        h = 1.0 / rh
+    h = max(h, 16 * np.finfo(float).eps * max(abs(t), 1e-300))
+    k = np.zeros((7, y.size))
+    k[0] = f0
+    nxt = 1
+    while t < tf:
+        hmin = 16 * np.finfo(float).eps * max(abs(t), 1e-300)
+        h = min(hmax, max(hmin, h))
+        if 1.1 * h >= tf - t:
+            h = tf - t
+        nofail = True
+        while True:
+            for s in range(1, 6):
+                k[s] = f(t + _C[s] * h, y + h * (_A[s, :s] @ k[:s]))
+            ynew = y + h * (_B5[:6] @ k[:6])
+            tnew = t + h
+            k[6] = f(tnew, ynew)
+            err = h * np.max(np.abs(_E @ k) / np.maximum(np.maximum(np.abs(y), np.abs(ynew)), thr))
+            if err > rtol:
+                if h <= hmin:
+                    raise RuntimeError("ode45_span: step size underflow")
+                if stats is not None:
+                    stats["nreject"] = stats.get("nreject", 0) + 1
+                if nofail:
+                    nofail = False
+                    h = max(hmin, h * max(0.1, 0.8 * (rtol / err) ** 0.2))
+                else:
+                    h = max(hmin, 0.5 * h)
+                continue
+            break
+        if stats is not None:
+            stats["naccept"] = stats.get("naccept", 0) + 1
+        while nxt < tspan.size and tspan[nxt] <= tnew:         # outputs inside (t, tnew]
+            if tspan[nxt] == tnew:
+                Y[nxt] = ynew
+            else:
+                s = (tspan[nxt] - t) / h
+                Y[nxt] = y + h * ((k.T @ _BI) @ np.array([s, s * s, s ** 3, s ** 4]))
+            nxt += 1
+        if nofail:
+            temp = 1.25 * (err / rtol) ** 0.2
+            hnext = h / temp if temp > 0.2 else 5.0 * h
+        else:
+            hnext = h
+        t, y = tnew, ynew
+        k[0] = k[6]
+        h = hnext
+    return Y

@@ -278,6 +278,31 @@ class Context:
         Z = np.transpose(Z, (0, 2, 1))
         return (Z[0], int(na[0]), int(nr[0]), int(st[0])) if single else (Z, na, nr, st)
 
+    def arm_simulate(self, params, mode, t, U, W=None, x0=None, Ts=0.0, rtol=1e-3, atol=1e-6):
+        """kp_arm_simulate: `batch` arm trials in one launch.  params: the Arm params dict (Nmods, nlinks, l, k, d, m, i, g,
+        ku); mode: 'zoh' / 'interp' / 'floor' / 'restart' (include/koopman_hip_arm.h); t (T,) shared by the batch;
+        U (batch, T, Nmods); W (batch, T, 2) or None (no load); x0 (batch, 2 Nlinks) or None (rest); Ts: the period of
+        'floor'.  Returns (X (batch, T_out, 2 Nlinks), naccept, nreject, status); a failed trial is NaN from its first
+        output not reached on, with status KP_ERR_NOT_CONVERGED."""
+        p = F.KpArmParams(int(params["Nmods"]), int(params["nlinks"]), *(float(params[f]) for f in ("l", "k", "d", "m", "i", "g", "ku")))
+        t = np.ascontiguousarray(np.asarray(t, dtype=np.float64).ravel())
+        U = np.ascontiguousarray(np.asarray(U, dtype=np.float64))
+        batch, T = U.shape[0], U.shape[1]
+        if t.size != T or U.ndim != 3:
+            raise ValueError("arm_simulate: U must be (batch, len(t), Nmods)")
+        if W is not None:
+            W = np.ascontiguousarray(np.broadcast_to(np.asarray(W, dtype=np.float64), (batch, T, 2)))
+        if x0 is not None:
+            x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64).reshape(batch, -1))
+        n = int(params["Nmods"]) * int(params["nlinks"])
+        Tout = T - 1 if mode == "interp" else T
+        X = np.zeros((batch, max(Tout, 0), 2 * n))
+        na = np.zeros(batch, dtype=np.int32); nr = np.zeros(batch, dtype=np.int32); st = np.zeros(batch, dtype=np.int32)
+        F.check(F.lib().kp_arm_simulate(self._h, C.byref(p), F.ARM_MODE[mode], batch, T, F.dptr(t), float(Ts), F.dptr(x0), F.dptr(U),
+                                        F.dptr(W), float(rtol), float(atol), F.dptr(X), na.ctypes.data_as(F.c_ip),
+                                        nr.ctypes.data_as(F.c_ip), st.ctypes.data_as(F.c_ip)), self._h)
+        return X, na, nr, st
+
     def lift_jacobian(self, basis, V):
         """kp_lift_jacobian: d econ_full / dv at the rows of V (rows x nvars; v = [zeta, u] for a nonlinear dictionary)
         -> (rows, N, nvars)."""
