@@ -14,8 +14,9 @@ from . import comm
 from .multi import Multi, MultiMpc
 from .arm import Arm
 from .arm_device import DeviceArm
+from .rsys_device import DeviceRsys
 from .kmpc import Kmpc, Ksim, ModelPlant
 from .ksysid import Ksysid, default_context, poly_exponent_table
 
-__all__ = ["Arm", "DeviceArm", "Basis", "Context", "Snapshots", "fit", "fit_gram", "fit_gram_sharded", "fit_refine", "fit_sharded", "Ksysid", "Kmpc", "Ksim", "ModelPlant", "Mpc", "KoopmanHipError", "default_context",
+__all__ = ["Arm", "DeviceArm", "DeviceRsys", "Basis", "Context", "Snapshots", "fit", "fit_gram", "fit_gram_sharded", "fit_refine", "fit_sharded", "Ksysid", "Kmpc", "Ksim", "ModelPlant", "Mpc", "KoopmanHipError", "default_context",
            "poly_exponent_table", "_ffi", "comm", "Multi", "MultiMpc"]

@@ -166,6 +166,17 @@ ARM_SIGNATURES = {
 }
 ARM_MODE = {"zoh": 0, "interp": 1, "floor": 2, "restart": 3}      # KP_ARM_SPAN_ZOH, _SPAN_INTERP, _SPAN_FLOOR, KP_ARM_RESTART
 
+# the random-system generator (include/koopman_hip_rsys.h)
+class KpRsysDims(C.Structure):
+    _fields_ = [("num_terms", C.c_int), ("degree_x", C.c_int), ("degree_u", C.c_int)]
+
+
+RSYS_SIGNATURES = {
+    "kp_rsys_simulate": (C.c_int, [vp, C.POINTER(KpRsysDims), C.c_int, C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_ip, c_ip, c_dp,
+                                   c_dp, c_dp, C.c_int, C.c_double, C.c_double, c_dp, c_ip, c_ip, c_ip, C.POINTER(vp)]),
+}
+RSYS_MODE = {"span": 0, "restart": 1}      # KP_RSYS_SPAN, KP_RSYS_RESTART
+
 _lib = None
 
 
@@ -177,7 +188,8 @@ def lib():
             raise OSError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(make -C koopman-realizations_amd/csrc)")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in (SIGNATURES | NMPC_SIGNATURES | OBSERVER_SIGNATURES | CT_SIGNATURES | ARM_SIGNATURES).items():
+        for name, (res, args) in (SIGNATURES | NMPC_SIGNATURES | OBSERVER_SIGNATURES | CT_SIGNATURES | ARM_SIGNATURES
+                                   | RSYS_SIGNATURES).items():
             fn = getattr(l, name)
             fn.restype, fn.argtypes = res, args
         _lib = l

@@ -527,6 +527,13 @@ extern "C" int kp_traj_create(kp_ctx* ctx, int nb, int ntrials, int T, int n, in
   return KP_OK;
 }
 
+// Internal (not in the C ABI): the four device blocks of a new object (0 Y, 1 U, 2 Yv, 3 Uv; layouts as kp_traj_upload),
+// marked as put.  A device producer (kp_rsys.hip) fills them on the context's stream and then calls kp_traj_finish.
+void kp_traj_device_blocks(kp_traj* t, double** blocks) {
+  blocks[0] = t->Y; blocks[1] = t->U; blocks[2] = t->Yv; blocks[3] = t->Uv;
+  t->have = 15;
+}
+
 extern "C" int kp_traj_put(kp_traj* t, int which, const double* host) {
   if (!t || !host || which < 0 || which > 3) return t ? t->ctx->fail(KP_ERR_ARG, "kp_traj_put: bad argument") : KP_ERR_ARG;
   kp_ctx* ctx = t->ctx;

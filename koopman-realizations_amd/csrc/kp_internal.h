@@ -13,6 +13,9 @@
 #define KP_MAX_VARS 32
 
 void kp_set_global_error(const std::string& s);
+// kp_batch.hip: the device blocks of a new kp_traj (0 Y, 1 U, 2 Yv, 3 Uv), marked as put - the caller fills them on the
+// context's stream, then kp_traj_finish scales them as for an upload
+void kp_traj_device_blocks(kp_traj* t, double** blocks);
 struct kp_comm_state;   // RCCL communicator of a multi-process run (kp_comm.hip)
 
 struct kp_stage;   // kp_upload.hip: copy stream, pinned staging ring and copy threads of the host -> HBM path

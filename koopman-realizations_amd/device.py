@@ -303,6 +303,43 @@ class Context:
                                         nr.ctypes.data_as(F.c_ip), st.ctypes.data_as(F.c_ip)), self._h)
         return X, na, nr, st
 
+    def rsys_simulate(self, mode, t, coeffs, pow_x, pow_u, input_gain, x0, U, hold=0, degree_x=None, degree_u=None,
+                      rtol=1e-3, atol=1e-6, want_traj=False, want_Y=True):
+        """kp_rsys_simulate: nsys x ntrials random-system trials in one launch.  mode: 'span' / 'restart'
+        (include/koopman_hip_rsys.h); t (T,); coeffs, pow_x, pow_u (nsys, num_terms); input_gain (nsys,); x0 (ntrials,),
+        shared by all systems; U (nsys, ntrials, T) with hold = 0, or the levels (nsys, ntrials, ceil(T / hold)) held
+        `hold` samples each.  degree_x / degree_u default to the largest power used.  Returns (Y (nsys, ntrials, T),
+        naccept, nreject, status), each (nsys, ntrials) but Y, and with want_traj=True also a finished Traj in the layout
+        of Rsys.save_data (the last trial validates) - None when a trial failed (status KP_ERR_NOT_CONVERGED).
+        want_Y=False: Y stays on the device (None is returned in its place)."""
+        t = np.ascontiguousarray(np.asarray(t, dtype=np.float64).ravel())
+        coeffs = np.ascontiguousarray(np.atleast_2d(np.asarray(coeffs, dtype=np.float64)))
+        nsys, nterms = coeffs.shape
+        px = np.ascontiguousarray(np.asarray(pow_x, dtype=np.int32).reshape(nsys, nterms))
+        pu = np.ascontiguousarray(np.asarray(pow_u, dtype=np.int32).reshape(nsys, nterms))
+        cu = np.ascontiguousarray(np.asarray(input_gain, dtype=np.float64).reshape(nsys))
+        x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64).ravel())
+        ntrials, T = x0.size, t.size
+        U = np.ascontiguousarray(np.asarray(U, dtype=np.float64))
+        width = T if hold == 0 else -(-T // max(int(hold), 1))
+        if U.shape != (nsys, ntrials, width):
+            raise ValueError(f"rsys_simulate: U must be ({nsys}, {ntrials}, {width})")
+        dims = F.KpRsysDims(int(nterms), int(px.max() if degree_x is None else degree_x), int(pu.max() if degree_u is None else degree_u))
+        Y = np.zeros((nsys, ntrials, T)) if want_Y else None
+        na = np.zeros((nsys, ntrials), dtype=np.int32); nr = np.zeros_like(na); st = np.zeros_like(na)
+        h = F.vp()
+        rc = F.lib().kp_rsys_simulate(self._h, C.byref(dims), F.RSYS_MODE[mode], nsys, ntrials, T, F.dptr(t), F.dptr(coeffs),
+                                      px.ctypes.data_as(F.c_ip), pu.ctypes.data_as(F.c_ip), F.dptr(cu), F.dptr(x0), F.dptr(U),
+                                      int(hold), float(rtol), float(atol), F.dptr(Y), na.ctypes.data_as(F.c_ip),
+                                      nr.ctypes.data_as(F.c_ip), st.ctypes.data_as(F.c_ip), C.byref(h) if want_traj else None)
+        if not want_traj:
+            F.check(rc, self._h)
+            return Y, na, nr, st
+        if rc == F.KP_ERR_NOT_CONVERGED:           # some trial failed: its status says which, and there is no object
+            return Y, na, nr, st, None
+        F.check(rc, self._h)
+        return Y, na, nr, st, Traj.from_handle(self, h)
+
     def lift_jacobian(self, basis, V):
         """kp_lift_jacobian: d econ_full / dv at the rows of V (rows x nvars; v = [zeta, u] for a nonlinear dictionary)
         -> (rows, N, nvars)."""
@@ -499,6 +536,20 @@ class Traj:
         self._h = F.vp()
         self._keep = []
         F.check(F.lib().kp_traj_create(ctx.handle, self.nb, self.ntrials, self.T, self.n, self.m, self.Tv, C.byref(self._h)), ctx.handle)
+        return self
+
+    @classmethod
+    def from_handle(cls, ctx: Context, h):
+        """Wrap an existing, finished kp_traj handle (made on the device, e.g. by kp_rsys_simulate); the object owns it from
+        now on.  The layout is read back with kp_traj_dims."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        ctx._children.add(self)
+        self._h = h if isinstance(h, F.vp) else F.vp(h)
+        self._keep = []
+        d = [C.c_int() for _ in range(6)]
+        F.check(F.lib().kp_traj_dims(self._h, *(C.byref(v) for v in d)), ctx.handle)
+        self.nb, self.ntrials, self.T, self.n, self.m, self.Tv = (v.value for v in d)
         return self
 
     def put(self, which, a):

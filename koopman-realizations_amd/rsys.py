@@ -5,6 +5,7 @@
                                          a_j / b_j = number of selected copies of x / u (selectors are
                                          0/1 over `degree_x` copies of x and `degree_u` copies of u)
   simulate_systems      Rsys.m:96-125   step inputs held `num_steps` samples, ode45 between samples
+  simulate_systems_ode45                the reference's own integration: ONE ode45 over the time vector (get_u rows)
   generate_input_steps  Rsys.m:136-150
   save_data             Rsys.m:182-216  -> list of data4sysid dicts {train: [...], val: [...]} (the last
                                          trial validates), the input format of `Ksysid` / `sweep.eval_system`
@@ -178,6 +179,71 @@ class Rsys:
             for j in range(num_trials):
                 l_ = i * num_trials + j
                 data[j][i] = {"t": tq.copy(), "y": Y[l_][:, None].copy(), "u": U[l_][:, None].copy()}
+        return data
+
+    @staticmethod
+    def get_u_row(t, tq):
+        """get_u's row (Rsys.m:128-133): the last index j with tq[j] <= t, clamped to [0, len(tq) - 1]."""
+        return min(max(int(np.searchsorted(tq, t, side="right")) - 1, 0), len(tq) - 1)
+
+    @staticmethod
+    def get_u(t, tq, uq):
+        """Rsys.m:128-133: the input row of time t."""
+        return uq[Rsys.get_u_row(t, tq)]
+
+    def _collect(self, s, u):
+        """System s's polynomial in x under the held input u: w[p] = sum_j c_j u^(b_j) [a_j = p] (+ c_u u at p = 0), the
+        arithmetic of simulate_systems_fast (and of kp_rsys_simulate) term by term."""
+        w = [0.0] * (self.degree_x + 1)
+        for c, a, b in zip(s["coeffs"], s["pow_x"], s["pow_u"]):
+            ub = 1.0
+            for _ in range(int(b)):
+                ub = ub * u
+            w[int(a)] = w[int(a)] + float(c) * ub
+        w[0] = w[0] + float(s["input_gain"]) * u
+        return w
+
+    def simulate_systems_ode45(self, t_end, Ts, num_trials, x0, inputs=None, lanes=None, rtol=1e-3, atol=1e-6):
+        """Rsys.m:96-125 as the reference integrates: ONE ode45 call over tq per trial (`arm.ode45_span`), the input of a
+        stage time chosen by get_u (the last sample at or before it), outputs from ode45's interpolant.  Returns
+        data[j][i] = {t, y, u} like simulate_systems (same draws, same layout).  inputs (num_sys, num_trials, len(tq)):
+        use these input rows instead of drawing them.  lanes: the (system, trial) pairs to integrate (default all; the
+        others are None).  Step counts land in self.last_stats ("naccept", "nreject": num_sys x num_trials).
+        Slow (tens of ms per trial): the yardstick of the device span mode, for small sets."""
+        from .arm import ode45_span
+        x0 = np.atleast_2d(np.asarray(x0, dtype=np.float64))
+        if x0.shape[0] == 1:
+            x0 = np.repeat(x0, num_trials, axis=0)
+        tq = np.arange(0.0, t_end + 0.5 * Ts, Ts)
+        ns = self.num_sys
+        if inputs is None:
+            inputs = np.stack([np.stack([self.generate_input_steps(tq, 50) for _ in range(num_trials)]) for _ in range(ns)])
+        inputs = np.asarray(inputs, dtype=np.float64)
+        todo = set((int(i), int(j)) for i, j in lanes) if lanes is not None else None
+        na = np.zeros((ns, num_trials), dtype=np.int64); nr = np.zeros_like(na)
+        data = [[None] * ns for _ in range(num_trials)]
+        for i, s in enumerate(self.systems):
+            for j in range(num_trials):
+                if todo is not None and (i, j) not in todo:
+                    continue
+                uq = inputs[i, j]
+                cache = {}
+
+                def f(t, x, s=s, uq=uq, cache=cache):
+                    u = float(self.get_u(t, tq, uq))
+                    if cache.get("u") != u:
+                        cache["u"], cache["w"] = u, self._collect(s, u)
+                    w = cache["w"]
+                    acc = w[-1]
+                    for p in range(len(w) - 2, -1, -1):
+                        acc = acc * x + w[p]
+                    x2 = x * x
+                    return np.exp(-(x2 * x2)) * acc - np.arctan(x)
+                st = {}
+                y = ode45_span(f, tq, x0[j], rtol=rtol, atol=atol, stats=st)
+                na[i, j], nr[i, j] = st.get("naccept", 0), st.get("nreject", 0)
+                data[j][i] = {"t": tq.copy(), "y": y, "u": uq[:, None].copy()}
+        self.last_stats = {"naccept": na, "nreject": nr}
         return data
 
     @staticmethod

@@ -281,40 +281,52 @@ def rand_models_sweep_arrays(Y, U, k, Yv, Uv, ctx, degrees=None, nested=True, tr
     """The batched sweep on already stacked raw trajectories: Y (nb, k T, n), U (nb, k T, m) = the k training trials of
     every system back to back, Yv / Uv (nb, Tv, ·) the validation trial (what `_stack_raw` builds from the reference's
     data4sysid structs; a generator or loader that produces the blocks directly skips that gathering)."""
-    from .device import Basis, Traj
-    from .ksysid import poly_exponent_table
-    degrees = degrees or MAX_DEGREE
-    n, m = Y.shape[2], U.shape[2]
+    from .device import Traj
     if traj is None:                                   # (else: the caller has uploaded these very blocks already)
         traj = Traj(ctx, Y, U, k, Yv, Uv)
-    out = {}
     try:
-        for mt in ("linear", "bilinear", "nonlinear"):
-            nv = n + (m if mt == "nonlinear" else 0)
-            D = degrees[mt]
-            basis = Basis(ctx, mt, n, m, [("poly", poly_exponent_table(nv, D)[nv:])], None)
-            try:
-                if nested and basis.W <= 16:          # all degrees from one pass over the data (sub-blocks of the degree-D Grams)
-                    err, st = traj.sweep_eval_nested(basis, D, 4.0 if mt == "nonlinear" else np.inf)      # lasso 4: evaluate_rand_models.m:122
-                    # a system whose batched fit failed (Gram not positive definite, lasso not converged) has no model: NaN,
-                    # as the reference's own `\` would propagate, instead of whatever the rollout made of it
-                    out[mt] = np.where(st != 0, np.nan, err[:, :, 0])
-                    # kernel time of this model type's Gram pass (kp_traj_gram_kernel), its width and pair count: bench line
-                    ctx.__dict__.setdefault("_sweep_gram", {})[mt] = (ctx.timer(0), basis.W, Y.shape[0] * (k * (Y.shape[1] // k - 1) - 1), ctx.timer(10))
-                    continue
-            finally:
-                basis.close()
-            rows = []
-            for j in range(1, D + 1):
-                basis = Basis(ctx, mt, n, m, [("poly", poly_exponent_table(nv, j)[nv:])], None)
-                try:
-                    err, st = traj.sweep_eval(basis, 4.0 if mt == "nonlinear" else np.inf)
-                    rows.append(np.where(st != 0, np.nan, err[:, 0]))
-                finally:
-                    basis.close()
-            out[mt] = np.stack(rows, axis=0)
+        return _sweep_traj_table(traj, ctx, Y.shape[2], U.shape[2], degrees, nested, Y.shape[0] * (k * (Y.shape[1] // k - 1) - 1))
     finally:
         traj.close()
+
+
+def rand_models_sweep_traj(traj, ctx, degrees=None, nested=True):
+    """The batched sweep on a Traj that is already resident on the device (DeviceRsys.simulate_to_traj, or any finished
+    kp_traj): the same table as `rand_models_sweep_arrays` on the same raw trajectories.  The caller keeps the object."""
+    return _sweep_traj_table(traj, ctx, traj.n, traj.m, degrees, nested, traj.nb * (traj.ntrials * (traj.T - 1) - 1))
+
+
+def _sweep_traj_table(traj, ctx, n, m, degrees, nested, npairs):
+    """Every (model type, degree) of evaluate_rand_models.m:38-43 on the resident trajectories `traj` (npairs: the
+    snapshot pairs of all systems, for the bench line)."""
+    from .device import Basis
+    from .ksysid import poly_exponent_table
+    degrees = degrees or MAX_DEGREE
+    out = {}
+    for mt in ("linear", "bilinear", "nonlinear"):
+        nv = n + (m if mt == "nonlinear" else 0)
+        D = degrees[mt]
+        basis = Basis(ctx, mt, n, m, [("poly", poly_exponent_table(nv, D)[nv:])], None)
+        try:
+            if nested and basis.W <= 16:          # all degrees from one pass over the data (sub-blocks of the degree-D Grams)
+                err, st = traj.sweep_eval_nested(basis, D, 4.0 if mt == "nonlinear" else np.inf)      # lasso 4: evaluate_rand_models.m:122
+                # a system whose batched fit failed (Gram not positive definite, lasso not converged) has no model: NaN,
+                # as the reference's own `\` would propagate, instead of whatever the rollout made of it
+                out[mt] = np.where(st != 0, np.nan, err[:, :, 0])
+                # kernel time of this model type's Gram pass (kp_traj_gram_kernel), its width and pair count: bench line
+                ctx.__dict__.setdefault("_sweep_gram", {})[mt] = (ctx.timer(0), basis.W, npairs, ctx.timer(10))
+                continue
+        finally:
+            basis.close()
+        rows = []
+        for j in range(1, D + 1):
+            basis = Basis(ctx, mt, n, m, [("poly", poly_exponent_table(nv, j)[nv:])], None)
+            try:
+                err, st = traj.sweep_eval(basis, 4.0 if mt == "nonlinear" else np.inf)
+                rows.append(np.where(st != 0, np.nan, err[:, 0]))
+            finally:
+                basis.close()
+        out[mt] = np.stack(rows, axis=0)
     return out
 
 
