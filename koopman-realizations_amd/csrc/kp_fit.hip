@@ -54,9 +54,6 @@ __device__ __forceinline__ double lane_bcast(double v, int lane) {
   return __hiloint2double(hi, lo);
 }
 
-#ifndef KP_CHOL_ABL
-#define KP_CHOL_ABL 0
-#endif
 #define CH_NT 512   // 8 waves: two per SIMD, 256 VGPRs each (the 8 x 8 micro tiles of the trailing update hold 64 accumulators)
 
 // 16 x 16 diagonal block at (k0, k0) by ONE wave, entirely in registers: lane r (< 16) owns row r; pivots and
@@ -223,7 +220,6 @@ __global__ __launch_bounds__(CH_NT) void kp_chol_kernel(double* __restrict__ A, 
     }
     CH_TICK(0);
     // L21 = A21 * L^-T by forward substitution, one thread per row (the block L and 1/diag are broadcast LDS reads)
-#if KP_CHOL_ABL != 3
     for (int r = tid; r < R; r += CH_NT) {
       double l[16];
 #pragma unroll
@@ -236,7 +232,6 @@ __global__ __launch_bounds__(CH_NT) void kp_chol_kernel(double* __restrict__ A, 
         A[(size_t)(k0 + c) * n + k0 + 16 + r] = l[c];   // L (lower); L' (upper) is filled in once at the end
       }
     }
-#endif
     __syncthreads();
     CH_TICK(1);
     // trailing update of the lower triangle in 8 x 8 micro tiles.  Look-ahead: the next diagonal block is updated first; then wave 0 factors that block while the other waves update the rest.
@@ -254,9 +249,7 @@ __global__ __launch_bounds__(CH_NT) void kp_chol_kernel(double* __restrict__ A, 
     __syncthreads();
     CH_TICK(2);
     if (wave == 0) {
-#if KP_CHOL_ABL != 2
       chol_diag_block(A, n, k0 + 16, D, Dd, &bad, odiag);
-#endif
     } else {
       // the triangle of ntb x ntb micro tiles is folded into an (ntb+1) x (ntb/2) rectangle; tiles (0,0),(1,0),(1,1) are done
       const int total = (ntb + 1) * (ntb / 2);
@@ -271,9 +264,7 @@ __global__ __launch_bounds__(CH_NT) void kp_chol_kernel(double* __restrict__ A, 
           tj = ntb - 1 - j;
         }
         if (ti <= 1) continue;                      // (0,0), (1,0), (1,1)
-#if KP_CHOL_ABL != 1
         chol_tile_update(A22, n, Lt, n, ti, tj, Pin);
-#endif
       }
     }
     if (prof && wave == 0) CH_TICK(3);       // wave 0: the diagonal block alone

@@ -13,9 +13,6 @@
 
 #include "kp_internal.h"
 
-#ifndef KP_ABLATE
-#define KP_ABLATE 0
-#endif
 #define KT 8  // snapshots per LDS tile (two k-steps of the 16x16x4 MFMA)
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
@@ -229,12 +226,9 @@ __global__ __launch_bounds__(256, 1) void kp_gram_kernel(GramArgs a) {
     // (1) prefetch raw tile t+2 into a register
     const RawRegs rawreg = load_raw(kt0 + t + 2);
     // (2) lift tile t+1 into the other Psi buffer
-#if KP_ABLATE != 1
     if (t + 1 < nkt) lift_tile((t + 1) & 1, (t + 1) & 1, kt0 + t + 1);
-#endif
     // (3) MFMA over tile t
     const double* P = sm + L.psi + (t & 1) * 2 * KT * a.Wp;
-#if KP_ABLATE != 2
     {
       // software-pipelined operand fetch: LDS reads run PF MFMAs ahead of their use
       constexpr int NM = (KT / 4) * NACC;
@@ -256,7 +250,6 @@ __global__ __launch_bounds__(256, 1) void kp_gram_kernel(GramArgs a) {
         acc[i % NACC] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[i], bv[i], acc[i % NACC], 0, 0, 0);
       }
     }
-#endif
     // (4) raw tile t+2 -> power-table buffer t&1 (last read while lifting tile t)
     store_raw(t & 1, rawreg);
     __syncthreads();

@@ -16,9 +16,6 @@
 
 #include "kp_internal.h"
 
-#ifndef KP_ABL
-#define KP_ABL 0   // timing-only ablations (results wrong): 1 no lift in loop, 2 also no raw store, 3 no MFMA
-#endif
 #define KT 8    // snapshots per LDS tile (two k-steps)
 #define NW 8    // waves per workgroup (two per SIMD: one wave's LDS/VALU issue hides behind the other's MFMAs)
 #define NTHR (64 * NW)
@@ -225,19 +222,13 @@ __global__ __launch_bounds__(NTHR, 2) void kp_gram2_kernel(Gram2Args a) {
         const int kk = step / NACC, q = step % NACC;
         if (step + PF < NSTEP) bvs[step + PF] = P[((step + PF) / NACC) * 4 * Wp + bo[(step + PF) % NACC]];
         const double bv = bvs[step];
-#if KP_ABL != 3
         acc[q][0] = __builtin_amdgcn_mfma_f64_4x4x4f64(af[kk][0], bv, acc[q][0], 0, 0, 0);
         acc[q][1] = __builtin_amdgcn_mfma_f64_4x4x4f64(af[kk][1], bv, acc[q][1], 0, 0, 0);
         acc[q][2] = __builtin_amdgcn_mfma_f64_4x4x4f64(af[kk][2], bv, acc[q][2], 0, 0, 0);
         acc[q][3] = __builtin_amdgcn_mfma_f64_4x4x4f64(af[kk][3], bv, acc[q][3], 0, 0, 0);
-#else
-        acc[q][0] += bv * af[kk][0];
-#endif
         // lift of the NEXT snapshot tile: chunk i reads at step i*SP, writes LAG steps later
-#if KP_ABL != 1 && KP_ABL != 2
         if (step % SP == 0 && step / SP < CPT) lift_read(step / SP, nxt);
         if (step >= LAG && (step - LAG) % SP == 0 && (step - LAG) / SP < CPT) lift_write((step - LAG) / SP, nxt);
-#endif
       }
 #pragma unroll
       for (int i = 0; i < CPT; ++i) {              // chunks that did not fit inside the MFMA loop (tiny NACC)
@@ -245,9 +236,7 @@ __global__ __launch_bounds__(NTHR, 2) void kp_gram2_kernel(Gram2Args a) {
         if (i * SP + LAG >= NSTEP) lift_write(i, nxt);
       }
     }
-#if KP_ABL != 2
     store_raw(cur, rawreg);                        // raw tile t+2 -> power table `cur` (read while lifting tile t)
-#endif
     __syncthreads();
   }
 

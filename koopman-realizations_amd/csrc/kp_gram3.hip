@@ -20,7 +20,7 @@
 // lift) and the tail mask lives in the power table's constant entry.
 //
 // Round 6 (0.396 -> 0.358 ms per 1e5 pairs at W = 336; what each step gave is in DESIGN.md 3.1 "Round 6", measured with the
-// timing-only builds of tools/build_abl3.sh: MFMAs and their operand reads alone take 0.305 ms):
+// timing-only builds (removed; see HISTORY.md): MFMAs and their operand reads alone take 0.305 ms):
 //  * m = 3: TWO weights per weighted A operand (TUP below) - 5 weight multiplies per A group and k-step instead of 9;
 //  * the power table of the tile after next is built INSIDE the MFMA loop by every thread, branch-free (x .. x^4 at a
 //    compile-time entry stride, raw value loaded a tile ahead; INL), not behind it with a run-time loop and exec masks;
@@ -30,9 +30,9 @@
 //    instead of the ds_read2_b64 pairs the compiler formed at half the LDS rate);
 //  * the lift's (item, snapshot pair) jobs dealt over 3 x 256 slots: three lift steps per tile instead of four;
 //  * the first three raw tiles requested in front of the one-time LDS setup.
-// Measured and NOT kept: lift stores as two ds_write_b64 at immediate offsets instead of ds_write2_b64 + v_add (slower), the
-// k-step's weights kept in registers across the wave's two A groups (slower), 7 quads per wave (147 spilled registers), the
-// items with three real factors gathered in the last wave so that the others skip a read and a multiply (branches and the
+// Measured and NOT kept: lift stores as two ds_write_b64 at immediate offsets instead of ds_write2_b64 + v_add (slower: 0.3718
+// against 0.3659 ms), the k-step's weights kept in registers across the wave's two A groups (slower), 7 quads per wave
+// (147 spilled registers), the items with three real factors gathered in the last wave so that the others skip a read and a multiply (branches and the
 // scattered stores cost more), B operands 2 / 4 steps ahead and the raw load behind other steps (no difference), cbsz / abid
 // (they do not broadcast blocks on v_mfma_f64_4x4x4_4b: tools/mfma_bcast_probe.hip).
 //
@@ -45,22 +45,6 @@
 
 #include "kp_internal.h"
 
-#ifndef KP_ABL3
-#define KP_ABL3 0
-#endif
-#ifndef KP_G3_ASMW
-#define KP_G3_ASMW 0    // 1: lift stores as 8-byte stores at immediate offsets (inline asm) instead of the compiler's ds_write2_b64 + v_add.
-                        // Measured SLOWER (0.3718 against 0.3659 ms): two store instructions cost the wave more than a v_add and one
-#endif
-#ifndef KP_G3_NLS
-#define KP_G3_NLS 3     // lift steps per tile: 3 = (item, snapshot pair) jobs dealt over 3 x 256 slots; 4 = item per thread, one step per pair
-#endif
-#ifndef KP_G3_KEEPWT
-#define KP_G3_KEEPWT 0   // 1: the k-step's weights stay in registers for the wave's second A group instead of being read again
-#endif
-#ifndef KP_G3_TBASM
-#define KP_G3_TBASM 1   // ... the table stores that way are faster (0.3640 against 0.3659 ms; four entries 80 bytes apart: no ds_write2 pairs them without an add)
-#endif
 #ifndef KP_RAW_STEP
 #define KP_RAW_STEP 1   // MFMA step of a tile behind which the raw loads of the tile after next are issued
 #endif
@@ -134,7 +118,7 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
   // INL (monomial dictionaries lifted in the kernel): the power table of the tile after next is built INSIDE the MFMA loop -
   // branch-free, four powers per raw value at a compile-time entry stride - instead of behind it (round 6: the end-of-tile
   // build with its run-time power loop, its exec-mask branches and its wait for the raw load cost 29 of 389 us, timing-only
-  // build KP_ABL3=8).  kp_gram3_applicable admits monomial dictionaries with powers <= 4 only (others: kp_gram2 / general kernel).
+  // build; removed, see HISTORY.md).  kp_gram3_applicable admits monomial dictionaries with powers <= 4 only (others: kp_gram2 / general kernel).
   constexpr bool INL = !EXT && !PRE;
   // Table layout (doubles): row r (raw rows, then the constant's row) at r * RB, its entry e at + e * PST3, KT3 snapshots each.
   // EXT keeps the dense id order of its recipes (RB = D entries).  INL: 4 entries per row and, when the table has the room, a row
@@ -204,7 +188,6 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
     }
     woff_ = PSI03 + (lvalid ? lside * YOFF3 + lcol : lwt ? WOFF3 + wslot(lw + 1) : SOFF3 + (tid & 31));
   };
-#if KP_G3_NLS == 3
   // The 4 (2 nfull + NWT - 1) (item, snapshot pair) jobs of a tile dealt over 3 x 256 slots: three lift steps per tile instead of
   // four (item = thread, one step per snapshot pair: 256 lanes for 177 items at N = 84).  A slot's snapshot pair is part of its
   // addresses, not an immediate: 12 address registers per thread instead of 4.  kp_gram3_applicable: 2 nfull + NWT - 1 <= 192.
@@ -223,11 +206,6 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
       ws[j] += 2 * ch * RS3;
     }
   }
-#else
-  int fa[NF3];
-  int woff;
-  item_setup(tid, fa, woff);
-#endif
 
   const int64_t kt0 = (int64_t)split * a.ktiles_per_split;
   const int64_t ktiles_total = (a.Ns + KT3 - 1) / KT3;
@@ -363,17 +341,12 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
     }
     const double x2 = xv * xv, x3 = x2 * xv, x4 = x2 * x2;
     const uint32_t tb_dst_b = tb_dst;                              // (an asm operand alone does not capture in a generic lambda)
-#if !KP_G3_TBASM
-    double* dstp = sm + BUF * POWBUF3 + tb_r * RB + ld_s;
-    dstp[0] = xv; dstp[PST3] = x2; dstp[2 * PST3] = x3; dstp[3 * PST3] = x4;
-    (void)tb_dst_b;
-#else
-    // (8-byte stores at immediate offsets from one address register: four entries 80 bytes apart, no ds_write2 pairs them without an add)
+    // (8-byte stores at immediate offsets from one address register: four entries 80 bytes apart, no ds_write2 pairs them without
+    // an add; 0.3640 against 0.3659 ms for the compiler's stores.  Not counted by the compiler: see lds_store_barrier)
     asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(tb_dst_b), "v"(xv), "n"((BUF * POWBUF3) * 8) : "memory");
     asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(tb_dst_b), "v"(x2), "n"((BUF * POWBUF3 + PST3) * 8) : "memory");
     asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(tb_dst_b), "v"(x3), "n"((BUF * POWBUF3 + 2 * PST3) * 8) : "memory");
     asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(tb_dst_b), "v"(x4), "n"((BUF * POWBUF3 + 3 * PST3) * 8) : "memory");
-#endif
   };
   auto store_tb = [&](auto buf_c) __attribute__((always_inline)) { store_tb_v(buf_c, tb_v, tb_tile - 1); };
   // the first three tiles' raw values are requested HERE, in front of the one-time LDS setup and its barriers: the setup runs in
@@ -446,7 +419,6 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
   };
 
   // ---- lift of a snapshot tile: power-table buffer B -> Psi buffer B, in pipelined chunks ----
-#if KP_G3_NLS == 3
   constexpr int NCH = NLS;                           // lift steps per tile
   double2 lf[NF3];
   auto lift_read = [&](int j, auto buf_c) __attribute__((always_inline)) {
@@ -460,42 +432,17 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
     sm[BUF * PSIBUF3 + ws[j]] = (lf[0].x * lf[1].x) * lf[2].x;
     sm[BUF * PSIBUF3 + ws[j] + RS3] = (lf[0].y * lf[1].y) * lf[2].y;
   };
-#else
-  constexpr int NCH = KT3 / 2;                       // chunks: snapshot pairs
-  double2 lf[NF3];
-  auto lift_read = [&](int ch, auto buf_c) __attribute__((always_inline)) {
-    constexpr int BUF = decltype(buf_c)::value;
-#pragma unroll
-    for (int f = 0; f < NF3; ++f)      // (RB, PST3 and CA are even: 16-byte aligned, one ds_read_b128)
-      lf[f] = *reinterpret_cast<const double2*>(__builtin_assume_aligned(&sm[BUF * POWBUF3 + fa[f] + 2 * ch], 16));
+  // Workgroup barrier behind LDS stores.  The table stores of store_tb_v are inline-assembly ds_write_b64: the compiler's
+  // waitcnt insertion does not count them, so a bare __syncthreads() would not wait for them.  Every barrier that publishes
+  // a table or a lifted tile goes through here: s_waitcnt lgkmcnt(0) first (the compiler's own counted waits only become
+  // more conservative), then the barrier.
+  // gfx9 s_waitcnt immediate: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt[5:4] in bits [15:14]
+  constexpr int WAIT_LGKM0 = 0xc07f;
+  static_assert(WAIT_LGKM0 == ((63 & 15) | (7 << 4) | (0 << 8) | ((63 >> 4) << 14)), "vmcnt = 63 and expcnt = 7 (no wait), lgkmcnt = 0");
+  auto lds_store_barrier = [&]() __attribute__((always_inline)) {
+    __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
+    __syncthreads();
   };
-  // The two stores of a chunk go out as ds_write_b64 with 16-bit immediate offsets from ONE address register (every (buffer, row)
-  // of the Psi region lies within 64 KB of it).  Left to the compiler they become a ds_write2_b64, whose 8-bit offsets reach 2 KB:
-  // a v_add_u32 per chunk for the base - a vector instruction in the MFMA stream (~5.5 cycles of it) - for the same LDS time
-  // (13 cycles against 2 x 6).  The compiler does not count these stores: the tile's barrier is preceded by an explicit
-  // s_waitcnt lgkmcnt(0) (wait_lds_stores), and its own counted waits only become more conservative.
-  uint32_t woff_b = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) double*)(sm + woff);
-  auto lift_write = [&](int ch, auto buf_c) __attribute__((always_inline)) {
-    constexpr int BUF = decltype(buf_c)::value;
-    const double v0 = (lf[0].x * lf[1].x) * lf[2].x, v1 = (lf[0].y * lf[1].y) * lf[2].y;
-#define KP_LIFT_STORE(CH)                                                                                                        \
-  case CH:                                                                                                                       \
-    asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(woff_b), "v"(v0), "n"((BUF * PSIBUF3 + (2 * CH) * RS3) * 8) : "memory");     \
-    asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(woff_b), "v"(v1), "n"((BUF * PSIBUF3 + (2 * CH + 1) * RS3) * 8) : "memory"); \
-    break;
-#if KP_G3_ASMW
-    switch (ch) {                                       // (ch is a constant once the tile loop is unrolled; the offset must be an immediate)
-      KP_LIFT_STORE(0) KP_LIFT_STORE(1) KP_LIFT_STORE(2) KP_LIFT_STORE(3)
-    }
-#else
-    sm[BUF * PSIBUF3 + woff + (2 * ch) * RS3] = v0;
-    sm[BUF * PSIBUF3 + woff + (2 * ch + 1) * RS3] = v1;
-#endif
-#undef KP_LIFT_STORE
-    static_assert(KT3 / 2 == 4, "one case per snapshot pair of a tile");
-  };
-#endif
-  auto wait_lds_stores = [&]() __attribute__((always_inline)) { __builtin_amdgcn_s_waitcnt(0xc07f); };   // lgkmcnt(0)
   using B0 = std::integral_constant<int, 0>;
   using B1 = std::integral_constant<int, 1>;
 
@@ -566,8 +513,7 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
   } else {
     if constexpr (INL) store_tb_v(B0{}, tb_v0, 0);
     else store_raw(B0{}, load_raw());
-    wait_lds_stores();
-    __syncthreads();
+    lds_store_barrier();
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
       lift_read(i, B0{});
@@ -575,18 +521,15 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
     }
     if constexpr (INL) store_tb_v(B1{}, tb_v1, 1);
     else store_raw(B1{}, load_raw());
-    wait_lds_stores();
-    __syncthreads();
+    lds_store_barrier();
     if (PCS) project(B0{});
   }
 
   constexpr int NSTEP = (KT3 / 4) * NQ;                 // quad steps (NWT MFMAs each) per snapshot tile
   constexpr int SP = NSTEP / NCH > 0 ? NSTEP / NCH : 1;
   constexpr int LAG = SP / 2 > 0 ? SP / 2 : 1;
-#ifndef KP_G3_PF
-#define KP_G3_PF 3
-#endif
-  constexpr int PF = NSTEP < KP_G3_PF ? NSTEP : KP_G3_PF;   // B operands requested this many quad steps ahead
+  constexpr int PF_AHEAD = 3;                           // (2 and 4 steps ahead measured the same)
+  constexpr int PF = NSTEP < PF_AHEAD ? NSTEP : PF_AHEAD;   // B operands requested this many quad steps ahead
 
   // one snapshot tile: MFMAs on Psi buffer CUR, lift of the next tile into buffer 1-CUR, raw prefetch two ahead.
   // QS = number of leading quads that use A group a0 (wave-uniform, selected once outside the loop).
@@ -610,11 +553,7 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
     auto weigh = [&](double av) __attribute__((always_inline)) {
 #pragma unroll
       for (int w = 0; w < NAW; ++w) {
-#if KP_ABL3 == 7 || KP_ABL3 == 11
-        aw[w] = av;
-#else
         aw[w] = (!TUP && w == 0) ? av : av * wt[w];
-#endif
       }
     };
 #pragma unroll
@@ -665,27 +604,14 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
       }
       if (QS < NQ && q == QS) weigh(av1);
       // fetch the weights one step before they are multiplied in (LDS reads are free, registers are not)
-#if !KP_G3_KEEPWT
       if (QS < NQ && QS > 1 && q == QS - 1) load_wt(kk);
-#endif
       if (q == NQ - 1 && kk + 1 < KT3 / 4) load_wt(kk + 1);
-#if KP_ABL3 != 6
       if (step + PF < NSTEP) {
         bvs[step + PF] = sm[PB + ((step + PF) / NQ) * 4 * RS3 + bo[(step + PF) % NQ]];
         if constexpr (TUP) bvs2[step + PF] = sm[PB + ((step + PF) / NQ) * 4 * RS3 + bo2[(step + PF) % NQ]];
       }
       const double bv = bvs[step];
       const double bv2 = TUP ? bvs2[step] : 0.0;
-#else
-      const double bv = bvs[step % PF];
-      const double bv2 = TUP ? bvs2[step % PF] : 0.0;
-#endif
-#if KP_ABL3 == 10
-      if constexpr (true) {
-#pragma unroll
-        for (int w = 0; w < NAW; ++w) asm volatile("" :: "v"(aw[w]), "v"(bv), "v"(bv2));
-      } else
-#endif
       if constexpr (TUP) {
         // accumulator 2 p + h: blocks b = (weight 2 p + (b >> 1), group 2 h + (b & 1) of the quad)
 #pragma unroll
@@ -697,16 +623,13 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
 #pragma unroll
         for (int w = 0; w < NWT; ++w) acc[q][w] = __builtin_amdgcn_mfma_f64_4x4x4f64(aw[w], bv, acc[q][w], 0, 0, 0);
       }
-#if KP_ABL3 != 1 && KP_ABL3 != 6 && KP_ABL3 != 11
       // one register set for the chunk in flight: the write of chunk i precedes the read of chunk i+1
       if constexpr (!PRE) {
         if (step >= LAG && (step - LAG) % SP == 0 && (step - LAG) / SP < NCH) lift_write((step - LAG) / SP, NXT{});
         if (step % SP == 0 && step / SP < NCH) lift_read(step / SP, NXT{});
       }
-#endif
       __builtin_amdgcn_sched_barrier(0);   // keep the hand-made software pipeline: no hoisting of later steps' LDS reads
     }
-#if KP_ABL3 != 1 && KP_ABL3 != 6 && KP_ABL3 != 11
     if constexpr (!PRE) {
 #pragma unroll
       for (int i = 0; i < NCH; ++i) {
@@ -714,15 +637,13 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
         if (i * SP + LAG >= NSTEP) lift_write(i, NXT{});
       }
     }
-#endif
-#if KP_ABL3 != 8 && KP_ABL3 != 11
-    if constexpr (PRE) store_pre(NXT{}, prereg);
-    else if constexpr (!INL) store_raw(cur_c, rawreg);
-#endif
-#if KP_ABL3 != 9 && KP_ABL3 != 11
-    if constexpr (!PRE) wait_lds_stores();
-    __syncthreads();
-#endif
+    if constexpr (PRE) {
+      store_pre(NXT{}, prereg);
+      __syncthreads();
+    } else {
+      if constexpr (!INL) store_raw(cur_c, rawreg);
+      lds_store_barrier();
+    }
     if (PCS) project(NXT{});
   };
   auto run_tiles = [&](auto qs_c) __attribute__((always_inline)) {
@@ -981,8 +902,8 @@ static bool gram3_prelift(const kp_basis* basis) {
 bool kp_gram3_applicable(const kp_basis* basis) {
   const BasisDev& b = basis->dev;
   if (getenv("KP_NO_GRAM3")) return false;
-  // the lift deals 4 (2 nfull + weights) (item, snapshot pair) jobs over 3 x 256 slots (KP_G3_NLS = 3)
-  if (KP_G3_NLS == 3 && 2 * b.nfull + (b.m + 1) * (b.m + 2) / 2 - 1 > 192) return false;
+  // the lift deals 4 (2 nfull + weights) (item, snapshot pair) jobs over 3 x 256 slots (NLS = 3 in kp_gram3_kernel)
+  if (2 * b.nfull + (b.m + 1) * (b.m + 2) / 2 - 1 > 192) return false;
   if (gram3_ext(basis))
     return b.model_type == KP_MODEL_BILINEAR && basis->ext_max_factors <= NF3 && b.nfull <= YOFF3 && b.m >= 1 && b.m <= 3 &&
            2 * (b.nzeta + b.m) * KT3 <= 256 &&
@@ -1109,16 +1030,12 @@ int kp_gram3_launch(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapshots* s,
                                         (const uint32_t*)basis->d_recipes, (const double*)basis->d_pcsT, pre_buf, pre_rl, ctx->stream));
   if (plan.wpw == 8) e = kp_gram6_launch_kernel(a, plan.nq, grid, ctx->stream);
   else switch (plan.nq) {
-#ifndef KP_G3_DEV            // (development builds instantiate the headline shape only: the file takes minutes otherwise)
     case 1: e = launch3<1>(a, BM, grid, lds, ctx->stream); break;
     case 2: e = launch3<2>(a, BM, grid, lds, ctx->stream); break;
     case 3: e = launch3<3>(a, BM, grid, lds, ctx->stream); break;
     case 4: e = launch3<4>(a, BM, grid, lds, ctx->stream); break;
     case 5: e = launch3<5>(a, BM, grid, lds, ctx->stream); break;
     default: e = launch3<6>(a, BM, grid, lds, ctx->stream); break;
-#else
-    default: e = launch3b<6, 3, false>(a, grid, lds, ctx->stream); break;
-#endif
   }
   KP_HIP(ctx, e);
   if (timed) KP_HIP(ctx, hipEventRecord(ev_end, ctx->stream));

@@ -61,8 +61,9 @@ __global__ __launch_bounds__(PRE_T) void kp_gram3_pcs_transpose_kernel(const dou
 //     without the 4-way bank conflict of the round-4 layout [entry][8 snapshots];
 //   ONE LDS-only barrier per round (__syncthreads() would also drain the memory counter: the loads just requested, the stores
 //   just issued).
-// Measured (1e5 pairs, 84 -> 27 components; tools/prelift_abl5.sh = timing-only builds through KP_PM_ABL, tools/prelift_phase_probe.py
-// = in-kernel cycle counters, KP_PM_ABL=32): **38 us against round 4's 65.**  The MFMAs alone are 17 us (168 per tile at 16.5
+// Measured (1e5 pairs, 84 -> 27 components; timing-only builds and in-kernel cycle counters, both removed: see HISTORY.md):
+// **38 us against round 4's 65**  (38.8 us under rocprofv3 once the timing-only kernel argument was gone; 39.9 us with it, same
+// session, parent's own repeats within 0.7 us).  The MFMAs alone are 17 us (168 per tile at 16.5
 // cycles: the floor of this instruction), the 67 MB of output another ~17 us of HBM writes beside them.  The way here, each
 // step measured:
 //   * every wave doing all steps in turn - one wave per tile (two waves per SIMD) or a pair of waves sharing a tile (three) -
@@ -80,14 +81,12 @@ __global__ __launch_bounds__(PRE_T) void kp_gram3_pcs_transpose_kernel(const dou
 //     will not move a read above an earlier store, so every MFMA pair waited for a read issued just in front of it), 39 us with
 //     the A operands requested four steps ahead in the source, 38 us with a scheduling barrier per step (the scheduler sank the
 //     table reads to their uses).  Consumer round now 4 300 cycles (3 000 of instructions) + 500 of stores, producer 5 000.
-// Measured late in round 5 (-DPM_NS=2 / 1: the same pairs in two / four INDEPENDENT workgroups per CU, each with its own barrier,
+// Measured late in round 5 (PM_NS = 2 / 1: the same pairs in two / four INDEPENDENT workgroups per CU, each with its own barrier,
 // the arrangement that pays for the dense products of kp_tn_gemm.h): 46.8 and 209 us against 38.9 - with fewer pairs per workgroup
 // the power tables and the raw loads are shared by fewer consumers, and at one pair the 128-register cap spills.
 // What would be next: two producers per slot (table per side) to take the producer off the critical path, and a second look at
 // what the consumer's 1 300 extra cycles per round are.
-#ifndef PM_NS
 #define PM_NS 4       // tiles (producer / consumer pairs) per workgroup
-#endif
 #define PM_T (128 * PM_NS)
 #define PM_WGPCU (4 / PM_NS)      // workgroups per CU (8 waves per CU either way)
 #define PM_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
@@ -103,7 +102,7 @@ template <int BM, int NK, int NRAW>
 __global__ __launch_bounds__(PM_T, PM_WGPCU) void kp_gram3_prelift_mfma_kernel(const double* __restrict__ alpha, const double* __restrict__ beta, const double* __restrict__ u,
                                                                         int64_t Ns, int64_t ktiles, int nzeta, int D, int nfull, int k_pcs, int N, int G4,
                                                                         const uint32_t* __restrict__ recipes, const double* __restrict__ pcsT,
-                                                                        double* __restrict__ out, int rl, int abl) {
+                                                                        double* __restrict__ out, int rl) {
   extern __shared__ double sm[];                        // per slot: tab[2][nid + 1][PM_ES] | utab[BM + 1][8] | psi[2][4 NK + 1][PM_CS]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -226,7 +225,7 @@ __global__ __launch_bounds__(PM_T, PM_WGPCU) void kp_gram3_prelift_mfma_kernel(c
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (the next call's inputs overwrite utab)
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      if (tile < ktiles && !(abl & 8)) {
+      if (tile < ktiles) {
         double* ot = out + tile * (int64_t)(KT3 * rl);
 #pragma unroll
         for (int m = 0; m < NRAW; ++m) {
@@ -249,16 +248,11 @@ __global__ __launch_bounds__(PM_T, PM_WGPCU) void kp_gram3_prelift_mfma_kernel(c
     load_raw(tile0 + 2 * tstep);
     PM_LDS_BARRIER();                                   // P1: Psi(0) and table(1) are there
     int it = 0;
-    long long pph[2] = {0, 0}, plast = (abl & 32) ? clock64() : 0;
     for (int64_t tb0 = (int64_t)blockIdx.x * PM_NS; tb0 < ktiles; tb0 += tstep, ++it) {   // (uniform trip count over the workgroup)
       table_and_entries(tile0 + (int64_t)(it + 2) * tstep, it & 1);      // table(it + 2) where table(it) was: lift(it) read it a round ago
       load_raw(tile0 + (int64_t)(it + 3) * tstep);
-      if (abl & 32) { const long long tn_ = clock64(); pph[0] += tn_ - plast; plast = tn_; }
       PM_LDS_BARRIER();
-      if (abl & 32) { const long long tn_ = clock64(); pph[1] += tn_ - plast; plast = tn_; }
     }
-    if ((abl & 32) && lane == 0 && (blockIdx.x == 0 || blockIdx.x == 200) && slot < 2)
-      printf("producer (%d, %d): table+entries+loads %lld  barrier %lld cycles, %d rounds\n", (int)blockIdx.x, slot, pph[0], pph[1], it);
   } else {
     // ================================================ consumer ================================================
     const int li = lane & 3, blk = (lane >> 2) & 3, kq = lane >> 4;
@@ -295,7 +289,6 @@ __global__ __launch_bounds__(PM_T, PM_WGPCU) void kp_gram3_prelift_mfma_kernel(c
     const int pc = 4 * blk + li;
     const int d_off = (kq >> 1) * 2 * rl + (kq & 1) + (nzeta + pc) * PES;             // + g * 4 rl + side * 4 G4 PES (+ 16 PES)
     dbl2 f0[4], f1[4], f2[4];
-    long long tph[3] = {0, 0, 0}, tlast = 0;
     // one micro-operation of the lift of the NEXT tile (table tn, Psi buffer pn): 24 per round of 64 items -
     // 12 reads, 4 + 4 pairs of multiplies, 4 stores
     auto lift_op = [&](auto slot_c, auto tn_c, auto pn_c) __attribute__((always_inline)) {
@@ -324,7 +317,6 @@ __global__ __launch_bounds__(PM_T, PM_WGPCU) void kp_gram3_prelift_mfma_kernel(c
       }(std::make_integer_sequence<int, 24 * NIT>{});
     }
     PM_LDS_BARRIER();                                   // P1: Psi(0) and table(1) are there
-    if (abl & 32) tlast = clock64();
     // one round with the parity of the CURRENT tile as a constant (buffer offsets are immediates)
     auto round = [&](auto par_c, int64_t tile) __attribute__((always_inline)) {
       constexpr unsigned P = decltype(par_c)::value;
@@ -352,8 +344,7 @@ __global__ __launch_bounds__(PM_T, PM_WGPCU) void kp_gram3_prelift_mfma_kernel(c
           __builtin_amdgcn_sched_barrier(0);            // (the scheduler sinks the table reads to their uses otherwise: each then waits out its LDS latency)
         }(), ...);
       }(std::make_integer_sequence<int, 4 * NK>{});
-      if (abl & 32) { const long long tn_ = clock64(); tph[0] += tn_ - tlast; tlast = tn_; }
-      if (tile < ktiles && !(abl & 4)) {
+      if (tile < ktiles) {
         double* ot = out + tile * (int64_t)(KT3 * rl);
 #pragma unroll
         for (int side = 0; side < 2; ++side)
@@ -364,9 +355,7 @@ __global__ __launch_bounds__(PM_T, PM_WGPCU) void kp_gram3_prelift_mfma_kernel(c
             if (pc + 16 < k_pcs) og[d_off + 16 * PES] = acc[side][g][1];
           }
       }
-      if (abl & 32) { const long long tn_ = clock64(); tph[1] += tn_ - tlast; tlast = tn_; }
       PM_LDS_BARRIER();
-      if (abl & 32) { const long long tn_ = clock64(); tph[2] += tn_ - tlast; tlast = tn_; }
     };
     int it = 0;
     for (int64_t tb0 = (int64_t)blockIdx.x * PM_NS; tb0 < ktiles; tb0 += tstep, ++it) {
@@ -374,8 +363,6 @@ __global__ __launch_bounds__(PM_T, PM_WGPCU) void kp_gram3_prelift_mfma_kernel(c
       if (it & 1) round(std::integral_constant<unsigned, 1>{}, tile);
       else round(std::integral_constant<unsigned, 0>{}, tile);
     }
-    if ((abl & 32) && lane == 0 && (blockIdx.x == 0 || blockIdx.x == 200) && slot < 2)
-      printf("consumer (%d, %d): mfma+lift %lld  stores %lld  barrier %lld cycles, %d rounds\n", (int)blockIdx.x, slot, tph[0], tph[1], tph[2], it);
   }
 }
 
@@ -397,7 +384,7 @@ static hipError_t prelift_mfma_launch(const double* alpha, const double* beta, c
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
   const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((ktiles + PM_NS - 1) / PM_NS, (int64_t)cus * PM_WGPCU));
   hipLaunchKernelGGL((kp_gram3_prelift_mfma_kernel<BM, NK, NRAW>), dim3((unsigned)grid), dim3(PM_T), lds, st, alpha, beta, u, Ns, ktiles, nzeta, D, nfull, k_pcs, N, G4,
-                     recipes, pcsT, out, rl, kp_abl_int("KP_PM_ABL"));
+                     recipes, pcsT, out, rl);
   return hipGetLastError();
 }
 

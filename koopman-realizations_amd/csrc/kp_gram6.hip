@@ -4,7 +4,7 @@
 // kp_gram3_kernel (kp_gram3.hip) gives every wave the raw A fragment psi_x and has it form the ten weighted copies
 // w_ab psi_x itself: 9 v_mul_f64 per (A group, k-step), 18-36 per wave and 8-snapshot tile beside 120 MFMAs - and on gfx950
 // nothing on the VALU overlaps the f64 MFMA stream of its SIMD (profiles/r01_coissue.txt).  A timing-only build without those
-// multiplies (KP_ABL3=7) runs the 1e5-pair, W = 336 launch in 0.360 instead of 0.395 ms.  Here the LIFT writes the weighted
+// multiplies (removed; see HISTORY.md) ran the 1e5-pair, W = 336 launch in 0.360 instead of 0.395 ms.  Here the LIFT writes the weighted
 // columns: a Psi row is [ten weighted copies of psi_x, column by column | psi_y | zero group], 11 x 84 + 4 doubles, so that every
 // MFMA operand - A as well as B - is one ds_read_b64 with an immediate offset and the MFMA loop holds no multiply at all.  That
 // row is 7.4 KB; two buffers of eight rows are 121 KB, which leaves room for ONE workgroup per CU - so it has eight waves

@@ -203,13 +203,6 @@ struct kp_snapshots {
 };
 // page-locked host scratch of at least `bytes` (contents not preserved across calls that grow it); nullptr on failure
 void* kp_pinned_scratch(kp_ctx* ctx, size_t bytes);
-// Timing-only ablation switches (KP_WIDE_NOWEIGHT, KP_PIV_ABL, KP_PM_ABL: they make results WRONG by design) exist only in builds
-// with -DKP_ABLATIONS (tools/*_abl*.sh); the shipped library does not look at those variables.
-#ifdef KP_ABLATIONS
-static inline int kp_abl_int(const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; }
-#else
-static inline int kp_abl_int(const char*) { return 0; }
-#endif
 void kp_stage_destroy(kp_ctx* ctx);
 void kp_host_free_all(kp_ctx* ctx);
 void kp_traj_pool_free(kp_ctx* ctx);

@@ -187,7 +187,7 @@ __global__ __launch_bounds__(NT) void kp_pivchol_panel_kernel(const double* __re
 //    candidates (lane l reads candidate l mod NW) - instead of a serial scan over them;
 //  * the pivot column comes from the trailing matrix in memory (one coalesced load, issued as soon as the pivot is known).
 // What a step costs (0.93 us at W = 336: 34 us per launch of 32): NOT that load - a timing-only build without it
-// (KP_PIV_ABL=1) takes the same time - but the step's own dependent instruction chain: two DPP reductions with their
+// (removed; see HISTORY.md) takes the same time - but the step's own dependent instruction chain: two DPP reductions with their
 // v_readlane / ballot tails, 1 / sqrt with two Newton steps, the products, at ~7 cycles per dependent vector instruction
 // (tools/clock_probe).  (Fetching the columns of the runner-up candidates ahead was built on the assumption that the load
 // bounds the step - the runner-up of step j is the pivot of step j + 1 in 192 of 251 steps on the arm data's W = 336 Gram -
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(NT) void kp_pivchol_panel_kernel(const double* __re
 template <int NT>
 __global__ __launch_bounds__(NT) void kp_pivchol_panel32_kernel(const double* __restrict__ A, int W, int k0, int nb, double rel_tol, double* __restrict__ L,
                                                                 double* __restrict__ dg, int* __restrict__ ipos, int* __restrict__ perm,
-                                                                PivState* __restrict__ stt, int abl) {
+                                                                PivState* __restrict__ stt) {
   extern __shared__ double Pn[];         // [32][W]
   __shared__ double red_v[2][NT / 64];
   __shared__ int red_i[2][NT / 64];
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(NT) void kp_pivchol_panel32_kernel(const double* __
     const int p = __builtin_amdgcn_readlane(ci, __ffsll((long long)mk) - 1);
     if (k == 0) d1 = pv;
     if (!(pv > rel_tol * d1) || !(pv > 0.0)) { stop = 1; return true; }
-    const double a = (abl & 1) ? (tid == p ? pv : 0.0) : A[irow + (size_t)p * W];   // in flight across the products below (abl: timing only)
+    const double a = A[irow + (size_t)p * W];   // in flight across the products below
     double rinv = __builtin_amdgcn_rsq(pv);
     rinv = rinv * (1.5 - 0.5 * pv * rinv * rinv);
     rinv = rinv * (1.5 - 0.5 * pv * rinv * rinv);
@@ -395,14 +395,13 @@ int kp_pivchol_solve_dev(kp_ctx* ctx, const double* G_dev, const double* C_dev, 
               : rpt == 1 ? kp_ensure_lds(lds1024, (const void*)kp_pivchol_panel_kernel<1024, 1>, lds)
                          : kp_ensure_lds(lds4096, (const void*)kp_pivchol_panel_kernel<1024, PC_RPT_MAX>, lds));
   const dim3 ugrid((W + 63) / 64, (W + 63) / 64);
-  static const int piv_abl = kp_abl_int("KP_PIV_ABL");      // timing-only ablations (bit 0: no pivot-column load; -DKP_ABLATIONS builds)
   auto run_panels = [&](int k_from, int k_to) -> int {
     for (int k0 = k_from; k0 < k_to; k0 += nb) {
       const int nbk = std::min(nb, W - k0);
       if (fast32 && nt == 512)
-        hipLaunchKernelGGL((kp_pivchol_panel32_kernel<512>), dim3(1), dim3(512), lds, s, (const double*)A, W, k0, nbk, rel_tol, L, dg, ipos, perm, stt, piv_abl);
+        hipLaunchKernelGGL((kp_pivchol_panel32_kernel<512>), dim3(1), dim3(512), lds, s, (const double*)A, W, k0, nbk, rel_tol, L, dg, ipos, perm, stt);
       else if (fast32)
-        hipLaunchKernelGGL((kp_pivchol_panel32_kernel<1024>), dim3(1), dim3(1024), lds, s, (const double*)A, W, k0, nbk, rel_tol, L, dg, ipos, perm, stt, piv_abl);
+        hipLaunchKernelGGL((kp_pivchol_panel32_kernel<1024>), dim3(1), dim3(1024), lds, s, (const double*)A, W, k0, nbk, rel_tol, L, dg, ipos, perm, stt);
       else if (nt == 512)
         hipLaunchKernelGGL((kp_pivchol_panel_kernel<512, 1>), dim3(1), dim3(512), lds, s, (const double*)A, W, k0, nbk, rel_tol, L, dg, ipos, perm, stt);
       else if (rpt == 1)

@@ -1,7 +1,6 @@
 #!/bin/bash
-# gram kernel timing versus quads per job (KP_GRAM3_NQ override); usage: g3_nq.sh "<NQ list>" [old]
+# gram kernel timing versus quads per job (KP_GRAM3_NQ override); usage: g3_nq.sh "<NQ list>"
 cd $GRAFT_REPO_ROOT
-[ "$2" = old ] && export KP_GRAM3_OLD=1
 for NQ in ${1:-8 7 6 5 4}; do KP_GRAM3_NQ=$NQ python - <<PY
 import sys, numpy as np
 sys.path.insert(0,'.')

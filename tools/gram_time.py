@@ -1,5 +1,5 @@
 """Kernel time of the fused lift+Gram launch alone (no solve): mean of the last launches of a queue of kp_fit_gram calls.
-Used with KP_LIB_PATH=<experimental build> for timing-only ablations (wrong Grams do not matter here)."""
+KP_LIB_PATH=<experimental build> times another build of the library (the Grams are not checked here)."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
