@@ -1,10 +1,12 @@
 """Command line: identify a Koopman model from a reference data file, without MATLAB.
 
     python -m koopman_realizations_amd sysid DATA.mat --model_type bilinear --obs_degree 3 [--dim_red]
-        [--time_type continuous] [--out model.npz]
+        [--time_type continuous] [--lasso 1 10 100 --metric euclid_mean] [--out model.npz]
 
 is example_sysid.m:22-65 (Ksysid constructor, train_models, validation of every `val` trial) with the options of
-Ksysid_setup.m; prints the validation errors and optionally stores the model matrices."""
+Ksysid_setup.m; prints the validation errors and optionally stores the model matrices.  With several --lasso values every
+candidate is validated on every trial (one device call, Ksysid.val_candidates), the candidate with the least --metric is
+chosen (Ksysid.select_model) and that one is reported and stored."""
 from __future__ import annotations
 
 import argparse
@@ -23,6 +25,8 @@ def main(argv=None):
     s.add_argument("--obs_degree", nargs="+", type=int, default=[3])
     s.add_argument("--snapshots", type=float, default=float("inf"))
     s.add_argument("--lasso", nargs="+", type=float, default=[float("inf")])
+    s.add_argument("--metric", default="euclid_mean", choices=["mean", "rmse", "nrmse", "euclid_mean", "unscaled_euclid_mean"],
+                   help="with several --lasso values: the validation error, averaged over the trials, that picks the model")
     s.add_argument("--delays", type=int, default=0)
     s.add_argument("--dim_red", action="store_true")
     s.add_argument("--loaded", action="store_true")
@@ -39,13 +43,24 @@ def main(argv=None):
                 lasso=a.lasso if len(a.lasso) > 1 else a.lasso[0], delays=a.delays, dim_red=a.dim_red, loaded=a.loaded,
                 time_type=a.time_type)
     ks.train_models()
-    val = {"linear": ks.val_model, "bilinear": ks.val_BLmodel, "nonlinear": ks.val_NLmodel}[a.model_type]
     p = ks.params
     print(f"{a.model_type} {a.time_type}-time model: n={p['n']} m={p['m']} nzeta={p['nzeta']} N={p['N']}  pairs={len(ks.snapshotPairs['alpha'])}")
-    for i, v in enumerate(ks.valdata):
-        e = val(ks.model, v)["error"]
-        print(f"val trial {i}: rmse {np.array2string(e['rmse'], precision=4)}  nrmse {np.array2string(e['nrmse'], precision=4)}  "
-              f"mean euclid {e['euclid_mean']:.5f}")
+    tab = ks.val_candidates()               # every candidate on every trial: one device call
+    many = isinstance(ks.candidates, list)
+
+    def lines(c, indent):
+        for i in range(len(ks.valdata)):
+            print(f"{indent}val trial {i}: rmse {np.array2string(tab['rmse'][c, i], precision=4)}  "
+                  f"nrmse {np.array2string(tab['nrmse'][c, i], precision=4)}  mean euclid {tab['euclid_mean'][c, i]:.5f}")
+
+    if many:
+        for c, lv in enumerate(tab["lasso"]):
+            print(f"candidate {c}: lasso {lv:g}" + ("  (diverged)" if tab["diverged"][c].any() else ""))
+            lines(c, "  ")
+        best, _ = ks.select_model(a.metric, tab)
+        print(f"chosen by {a.metric}: candidate {best} (lasso {tab['lasso'][best]:g})")
+    else:
+        lines(0, "")
     if a.out:
         m = ks.model
         np.savez(a.out, **{k: np.asarray(m[k]) for k in ("A", "B", "C", "K", "Kf", "M") if k in m},

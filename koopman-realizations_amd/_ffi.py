@@ -177,6 +177,13 @@ RSYS_SIGNATURES = {
 }
 RSYS_MODE = {"span": 0, "restart": 1}      # KP_RSYS_SPAN, KP_RSYS_RESTART
 
+# the validation table (include/koopman_hip_validate.h)
+VALIDATE_SIGNATURES = {
+    "kp_validate": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_dp, c_dp, C.c_int,
+                              C.POINTER(C.c_int64), c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int, c_dp, c_ip, c_dp]),
+}
+VALIDATE_CHUNK = 128               # KP_VALIDATE_CHUNK
+
 _lib = None
 
 
@@ -189,7 +196,7 @@ def lib():
                           "(make -C koopman-realizations_amd/csrc)")
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in (SIGNATURES | NMPC_SIGNATURES | OBSERVER_SIGNATURES | CT_SIGNATURES | ARM_SIGNATURES
-                                   | RSYS_SIGNATURES).items():
+                                   | RSYS_SIGNATURES | VALIDATE_SIGNATURES).items():
             fn = getattr(l, name)
             fn.restype, fn.argtypes = res, args
         _lib = l

@@ -375,6 +375,49 @@ class Context:
                                         st.ctypes.data_as(F.c_ip)), self._h)
         return what, res, st
 
+    def validate(self, basis, model_type, models, trials, n, nw, yfactor, want_sim=False):
+        """kp_validate: every model rolled out over every trial in one launch, the errors of get_error reduced on the device.
+        basis: the unloaded dictionary; models: a list of (A, B) (linear, bilinear; loaded models at their full width
+        N (nw + 1)) or of Kf (nonlinear); trials: a list of (zeta0 (nzeta), U (T x m), Yreal (T x n), Wl (T x nw) or None),
+        the rows after the nd shift; yfactor (n): the factors of scaleup.y.  Returns (err (nmod, ntr, 3 n + 2):
+        [mean | rmse | nrmse | euclid_mean | unscaled euclid_mean], status (nmod, ntr): 1 where the simulated outputs left
+        the finite range, sim: a list per model of a list per trial of T x n arrays, or None)."""
+        N, m, nz, n, nw = basis.N, basis.m, basis.nzeta, int(n), int(nw)
+        NL = N * (nw + 1)
+        nmod, ntr = len(models), len(trials)
+        if model_type == "nonlinear":
+            A = np.ascontiguousarray(np.stack([np.asarray(k, dtype=np.float64).reshape(nz, NL).T for k in models]))
+            B = None
+        else:
+            mb = m * NL if model_type == "bilinear" else m
+            A = np.ascontiguousarray(np.stack([np.asarray(a, dtype=np.float64).reshape(NL, NL).T for a, _ in models]))
+            B = np.ascontiguousarray(np.stack([np.asarray(b, dtype=np.float64).reshape(NL, mb).T for _, b in models]))
+        Us = [np.asarray(u, dtype=np.float64).reshape(-1, m) for _, u, _, _ in trials]
+        Ys = [np.asarray(y, dtype=np.float64).reshape(-1, n) for _, _, y, _ in trials]
+        lens = [y.shape[0] for y in Ys]
+        if any(u.shape[0] != T for u, T in zip(Us, lens)):
+            raise ValueError("every trial needs as many input rows as output rows")
+        off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(lens)]), dtype=np.int64)
+        rows = int(off[-1])
+        z0 = F.fcol(np.stack([np.asarray(z, dtype=np.float64).reshape(nz) for z, _, _, _ in trials]))
+        U = F.fcol(np.vstack(Us)); Y = F.fcol(np.vstack(Ys))
+        W = None
+        if nw > 0:
+            Ws = [np.asarray(w, dtype=np.float64).reshape(-1, nw) for _, _, _, w in trials]
+            if any(w.shape[0] != T for w, T in zip(Ws, lens)):
+                raise ValueError("every trial needs as many load rows as output rows")
+            W = F.fcol(np.vstack(Ws))
+        fac = np.ascontiguousarray(np.broadcast_to(np.asarray(yfactor, dtype=np.float64), (n,)))
+        err = np.zeros((nmod, ntr, 3 * n + 2)); st = np.zeros((nmod, ntr), dtype=np.int32)
+        S = np.zeros((nmod, n, rows)) if want_sim else None
+        F.check(F.lib().kp_validate(self._h, basis.handle, F.MODEL[model_type], N, m, n, nz, nw, nmod, F.dptr(A), F.dptr(B), ntr,
+                                    off.ctypes.data_as(C.POINTER(C.c_int64)), F.dptr(z0), F.dptr(U), F.dptr(Y), F.dptr(W),
+                                    F.dptr(fac), int(bool(want_sim)), F.dptr(err), st.ctypes.data_as(F.c_ip), F.dptr(S)), self._h)
+        sim = None
+        if want_sim:
+            sim = [[np.ascontiguousarray(S[i, :, off[q]:off[q + 1]].T) for q in range(ntr)] for i in range(nmod)]
+        return err, st, sim
+
     def qp_solve(self, H, f, A, b):
         """quadprog_gurobi(H,f,A,b) shim: NaN vector on failure (quadprog_gurobi.m:22-23)."""
         H = F.fcol(H); A = F.fcol(A)

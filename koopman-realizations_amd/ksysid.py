@@ -782,6 +782,141 @@ class Ksysid:
             zs = self.ctx.rollout_nl(self.basis_dev, model["Kf"], zetareal[0], ureal)   # one launch for the whole trial
         return self._results(t, ureal, zs[:, :self.params["n"]], yreal)
 
+    # ---- the validation table: every candidate on every trial (Ksysid.m:1928-1972 over a lasso grid) ----------------
+    def _val_one(self, model, valdata):
+        return {"nonlinear": self.val_NLmodel, "bilinear": self.val_BLmodel, "linear": self.val_model}[self.model_type](model, valdata)
+
+    def _val_table_loop(self, models, trials, want_sim):
+        """The table by one val_* call per (model, trial): continuous time, and shapes kp_validate refuses."""
+        n = self.params["n"]
+        nmod, ntr = len(models), len(trials)
+        tab = {k: np.zeros((nmod, ntr, n)) for k in ("mean", "rmse", "nrmse")}
+        tab.update({k: np.zeros((nmod, ntr)) for k in ("euclid_mean", "unscaled_euclid_mean")})
+        tab["diverged"] = np.zeros((nmod, ntr), dtype=bool)
+        sim = [[None] * ntr for _ in range(nmod)]
+        for i, mod in enumerate(models):
+            for q, v in enumerate(trials):
+                res = self._val_one(mod, v)
+                e = res["error"]
+                for k in ("mean", "rmse", "nrmse", "euclid_mean"):
+                    tab[k][i, q] = e[k]
+                tab["unscaled_euclid_mean"][i, q] = e["unscaled"]["euclid_mean"]
+                tab["diverged"][i, q] = not np.all(np.isfinite(res["sim"]["y"]))
+                sim[i][q] = np.asarray(res["sim"]["y"])
+        if want_sim:
+            tab["sim"] = sim
+        return tab
+
+    def val_candidates(self, models=None, valdata=None, want_sim=False):
+        """The validation table of valNplot_model (Ksysid.m:1928-1972) run for every candidate: each model rolled out over
+        each validation trial and the errors of get_error (:1886-1897), in ONE device call (kp_validate: models and trials
+        uploaded once, one launch for the nmod x ntr rollouts with the load of every step, errors reduced in the kernel).
+        models: a model dict or a list of them (default: self.candidates, else [self.model]); valdata: a trial or a list
+        (default self.valdata; scaled, as val_model takes them).  Returns a dict of arrays: mean, rmse, nrmse
+        (nmod x ntr x n), euclid_mean, unscaled_euclid_mean (nmod x ntr), diverged (bool: the simulated outputs left the
+        finite range; the errors are then Inf / NaN, as MATLAB gives silently), lasso (nmod) when every model carries it,
+        and with want_sim sim[i][q]: the T_q x n simulated outputs.  Continuous-time models, and shapes the kernel refuses
+        (its LDS limits), go through the per-trial val_model / val_BLmodel / val_NLmodel loop and fill the same dict."""
+        if models is None:
+            models = self.candidates if self.candidates is not None else self.model
+        if models is None:
+            raise ValueError("no model: call train_models first")
+        models = [models] if isinstance(models, dict) else list(models)
+        if valdata is None:
+            valdata = self.valdata
+        trials = [valdata] if isinstance(valdata, dict) else list(valdata)
+        if not models or not trials:
+            raise ValueError("val_candidates needs at least one model and one trial")
+        tab = None
+        if self.time_type != "continuous":
+            p = self.params; n, nw = p["n"], p["nw"]
+            packed = []
+            for v in trials:
+                _, yreal, ureal, zetareal = self._val_common(v)
+                w = np.asarray(v["w"], dtype=np.float64).reshape(len(np.ravel(v["t"])), -1)[p["nd"]:] if self.loaded else None
+                packed.append((zetareal[0], ureal, yreal, w))
+            mods = [mo["Kf"] for mo in models] if self.model_type == "nonlinear" else [(mo["A"], mo["B"]) for mo in models]
+            try:
+                err, st, sim = self.ctx.validate(self.basis_dev, self.model_type, mods, packed, n, nw, p["scale"]["y_factor"], want_sim)
+            except F.KoopmanHipError as e:
+                if e.code != F.KP_ERR_ARG:
+                    raise
+            else:
+                tab = {"mean": err[:, :, :n].copy(), "rmse": err[:, :, n:2 * n].copy(), "nrmse": err[:, :, 2 * n:3 * n].copy(),
+                       "euclid_mean": err[:, :, 3 * n].copy(), "unscaled_euclid_mean": err[:, :, 3 * n + 1].copy(),
+                       "diverged": st != 0}
+                if want_sim:
+                    tab["sim"] = sim
+        if tab is None:
+            tab = self._val_table_loop(models, trials, want_sim)
+        if all("lasso" in mo for mo in models):
+            tab["lasso"] = np.array([float(mo["lasso"]) for mo in models])
+        return tab
+
+    def valNplot_model(self, model_id=None, saveask=False, plot_on=False):
+        """Ksysid.m:1928-1972 without the plots and the save dialog: the chosen candidate validated on every trial of
+        self.valdata (one device call, val_candidates).  model_id: None - the single candidate, or the first of a list
+        (:1939-1947) - or the 0-based index into self.candidates.  Returns (results, err): per trial the dict val_model
+        returns and the dict get_error returns."""
+        if plot_on or saveask:
+            raise NotImplementedError("valNplot_model: plotting and the save dialog are not part of this mirror (plot_on / saveask)")
+        cands = self.candidates
+        if cands is None:
+            raise ValueError("no candidates: call train_models first")
+        if isinstance(cands, dict):
+            if model_id not in (None, 0):
+                raise IndexError("there is a single candidate: model_id must be None or 0")
+            mod = cands
+        elif model_id is None:
+            mod = cands[0]
+        else:
+            if int(model_id) != model_id or not 0 <= int(model_id) < len(cands):
+                raise IndexError(f"model_id must be an index into the {len(cands)} candidates")
+            mod = cands[int(model_id)]
+        tab = self.val_candidates(mod, self.valdata, want_sim=True)
+        results, errs = [], []
+        for q, v in enumerate(self.valdata):
+            t, yreal, ureal, _ = self._val_common(v)
+            ysim = tab["sim"][0][q]
+            res = {"t": t, "sim": {"t": t, "u": ureal, "y": ysim}, "real": {"t": t, "u": ureal, "y": yreal}}
+            if self.loaded and self.model_type != "nonlinear":                  # :1707-1710
+                res["sim"]["w"] = res["real"]["w"] = np.asarray(v["w"], dtype=np.float64).reshape(len(np.ravel(v["t"])), -1)[self.params["nd"]:]
+            with np.errstate(over="ignore", invalid="ignore"):
+                d = ysim - yreal
+                err = {"abs": np.abs(d), "mean": tab["mean"][0, q], "rmse": tab["rmse"][0, q], "nrmse": tab["nrmse"][0, q],
+                       "euclid": np.sqrt((d ** 2).sum(axis=1)), "euclid_mean": float(tab["euclid_mean"][0, q]),
+                       "unscaled": {"euclid": np.sqrt(((d * self.params["scale"]["y_factor"]) ** 2).sum(axis=1)),
+                                    "euclid_mean": float(tab["unscaled_euclid_mean"][0, q])}}
+            res["error"] = err
+            results.append(res); errs.append(err)
+        return results, errs
+
+    _TABLE_METRICS = ("mean", "rmse", "nrmse", "euclid_mean", "unscaled_euclid_mean")
+
+    def select_model(self, metric="euclid_mean", table=None):
+        """The choice the reference leaves to the user (Ksysid.m:1384-1386): the candidate whose `metric`, averaged over the
+        validation trials (and the outputs, for mean / rmse / nrmse), is least.  Candidates that diverged on a trial, or
+        whose average is NaN, rank last.  table: a val_candidates result (default: computed now).  Sets self.model and
+        returns (index, table); ValueError when no candidate stays finite."""
+        if metric not in self._TABLE_METRICS:
+            raise ValueError(f"metric must be one of {self._TABLE_METRICS}")
+        if table is None:
+            table = self.val_candidates()
+        cands = self.candidates if self.candidates is not None else self.model
+        cands = [cands] if isinstance(cands, dict) else list(cands or [])
+        vals = np.asarray(table[metric], dtype=np.float64)
+        nmod = vals.shape[0]
+        if len(cands) != nmod:
+            raise ValueError(f"the table has {nmod} models, the object {len(cands)} candidates")
+        with np.errstate(invalid="ignore", over="ignore"):
+            score = vals.reshape(nmod, -1).mean(axis=1)
+        bad = np.asarray(table["diverged"], dtype=bool).reshape(nmod, -1).any(axis=1) | ~np.isfinite(score)
+        if bad.all():
+            raise ValueError("every candidate diverged on the validation trials")
+        best = int(np.argmin(np.where(bad, np.inf, score)))
+        self.model = cands[best]
+        return best, table
+
     # ---- load observer (Ksysid.m:1975-2139) ------------------------------------------------------------
     def _observer_model(self):
         """The model the observer regresses with, after the reference's limits: loaded, linear or bilinear, nd = 0."""
