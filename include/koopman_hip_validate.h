@@ -43,6 +43,35 @@ int kp_validate(kp_ctx* ctx, const kp_basis* basis, int model_type, int N, int m
                 const double* Yreal, const double* Wl, const double* yfactor, int want_sim, double* err_out,
                 int* status_out, double* Ysim);
 
+enum {
+  KP_VALIDATE_CT_CHUNK = 32,     /* samples whose inputs and outputs one workgroup of kp_validate_ct stages at a time */
+  KP_VALIDATE_CT_STAGE = 8192    /* doubles of A, Kf or the bilinear A + sum_i u_i B_i that kp_validate_ct keeps in LDS */
+};
+
+/* ---- validation table of continuous-time models (kp_validate_ct.hip; the same loop over val_model :1679-1683, val_BLmodel
+ * :1777-1781 or val_NLmodel :1849-1856 with time_type = 'continuous') ----
+ * kp_validate_ct: kp_validate for models of z' = A z + B u_j (linear), z' = (A + sum_i u_ji B_i) z (bilinear) or
+ *   zeta' = Kf econ_full([zeta; u_j]) (nonlinear, lifted in the kernel at every stage): every sample interval is integrated
+ *   over [0, Ts] with the input of row j held, from the end point of the previous one, by ode45's Dormand-Prince 5(4) pair
+ *   with the step control of kp_rollout_ct / kp_rollout_nl_ct (koopman_hip_ct.h; rtol = RelTol, atol = AbsTol).
+ *   basis, model_type, N, m, n, nzeta, the models A and B, trial_off, zeta0, U, Yreal, yfactor, want_sim, err_out and Ysim:
+ *   as kp_validate.  nw must be 0 and Wl is not read (Ksysid refuses loaded continuous-time models).
+ *   ysim = the first n entries of the state; row 0 of ysim is row 0 of Yreal (:1654).
+ *   A failed integration (step-size underflow, more than 100000 steps in one interval, a non-finite state) is data, not an
+ *   error: the samples from the failing one on are NaN, status_out (nmod x ntr) is 1 - as it is whenever a simulated output
+ *   is not finite - the pair's errors are what IEEE arithmetic gives, and the call returns KP_OK.
+ *   naccept / nreject (nmod x ntr, may be NULL): accepted / rejected steps over the whole rollout of a pair.
+ *   Every pair's numbers depend on that pair alone: they are the same bits alone or in any batch.
+ *   Limits (KP_ERR_ARG): nw != 0; Ts, rtol or atol not positive and finite; N > 512; n > N (nonlinear: n > nzeta); 11 state
+ *   and stage vectors, the error sums, one chunk of KP_VALIDATE_CT_CHUNK samples - (m + 2 n + 2) doubles per sample - and
+ *   B u (N) or, for a nonlinear model, the dictionary scratch (nvars + nfull + N) must fit 160 KB of LDS.  A matrix of at
+ *   most KP_VALIDATE_CT_STAGE doubles that fits beside them is staged there; a larger A or Kf is read from memory, a larger
+ *   bilinear A + sum_i u_i B_i lives in a per-pair slice of device scratch (nmod ntr N N doubles). */
+int kp_validate_ct(kp_ctx* ctx, const kp_basis* basis, int model_type, int N, int m, int n, int nzeta, int nw, int nmod,
+                   const double* A, const double* B, int ntr, const int64_t* trial_off, const double* zeta0, const double* U,
+                   const double* Yreal, const double* Wl, const double* yfactor, int want_sim, double Ts, double rtol,
+                   double atol, double* err_out, int* status_out, double* Ysim, int* naccept, int* nreject);
+
 #ifdef __cplusplus
 }
 #endif

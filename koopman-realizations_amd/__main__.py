@@ -30,7 +30,8 @@ def main(argv=None):
     s.add_argument("--delays", type=int, default=0)
     s.add_argument("--dim_red", action="store_true")
     s.add_argument("--loaded", action="store_true")
-    s.add_argument("--time_type", default="discrete", choices=["discrete", "continuous"])
+    s.add_argument("--time_type", default="discrete", choices=["discrete", "continuous"],
+                   help="continuous: models of the matrix logarithm, validated by ode45 per sample interval (also one device call)")
     s.add_argument("--device", type=int, default=0)
     s.add_argument("--out", default=None, help="write the model (A, B, C, K, scale) to this .npz")
     a = ap.parse_args(argv)

@@ -181,8 +181,13 @@ RSYS_MODE = {"span": 0, "restart": 1}      # KP_RSYS_SPAN, KP_RSYS_RESTART
 VALIDATE_SIGNATURES = {
     "kp_validate": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_dp, c_dp, C.c_int,
                               C.POINTER(C.c_int64), c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int, c_dp, c_ip, c_dp]),
+    "kp_validate_ct": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_dp, c_dp, C.c_int,
+                                 C.POINTER(C.c_int64), c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int, C.c_double, C.c_double, C.c_double,
+                                 c_dp, c_ip, c_dp, c_ip, c_ip]),
 }
 VALIDATE_CHUNK = 128               # KP_VALIDATE_CHUNK
+VALIDATE_CT_CHUNK = 32             # KP_VALIDATE_CT_CHUNK
+VALIDATE_CT_STAGE = 8192           # KP_VALIDATE_CT_STAGE
 
 _lib = None
 

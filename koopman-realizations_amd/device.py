@@ -375,16 +375,11 @@ class Context:
                                         st.ctypes.data_as(F.c_ip)), self._h)
         return what, res, st
 
-    def validate(self, basis, model_type, models, trials, n, nw, yfactor, want_sim=False):
-        """kp_validate: every model rolled out over every trial in one launch, the errors of get_error reduced on the device.
-        basis: the unloaded dictionary; models: a list of (A, B) (linear, bilinear; loaded models at their full width
-        N (nw + 1)) or of Kf (nonlinear); trials: a list of (zeta0 (nzeta), U (T x m), Yreal (T x n), Wl (T x nw) or None),
-        the rows after the nd shift; yfactor (n): the factors of scaleup.y.  Returns (err (nmod, ntr, 3 n + 2):
-        [mean | rmse | nrmse | euclid_mean | unscaled euclid_mean], status (nmod, ntr): 1 where the simulated outputs left
-        the finite range, sim: a list per model of a list per trial of T x n arrays, or None)."""
-        N, m, nz, n, nw = basis.N, basis.m, basis.nzeta, int(n), int(nw)
+    @staticmethod
+    def _validate_pack(basis, model_type, models, trials, n, nw):
+        """The arguments of kp_validate / kp_validate_ct: (A, B, off, z0, U, Y, W) in the layouts of the header."""
+        N, m, nz = basis.N, basis.m, basis.nzeta
         NL = N * (nw + 1)
-        nmod, ntr = len(models), len(trials)
         if model_type == "nonlinear":
             A = np.ascontiguousarray(np.stack([np.asarray(k, dtype=np.float64).reshape(nz, NL).T for k in models]))
             B = None
@@ -398,7 +393,6 @@ class Context:
         if any(u.shape[0] != T for u, T in zip(Us, lens)):
             raise ValueError("every trial needs as many input rows as output rows")
         off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(lens)]), dtype=np.int64)
-        rows = int(off[-1])
         z0 = F.fcol(np.stack([np.asarray(z, dtype=np.float64).reshape(nz) for z, _, _, _ in trials]))
         U = F.fcol(np.vstack(Us)); Y = F.fcol(np.vstack(Ys))
         W = None
@@ -407,6 +401,19 @@ class Context:
             if any(w.shape[0] != T for w, T in zip(Ws, lens)):
                 raise ValueError("every trial needs as many load rows as output rows")
             W = F.fcol(np.vstack(Ws))
+        return A, B, off, z0, U, Y, W
+
+    def validate(self, basis, model_type, models, trials, n, nw, yfactor, want_sim=False):
+        """kp_validate: every model rolled out over every trial in one launch, the errors of get_error reduced on the device.
+        basis: the unloaded dictionary; models: a list of (A, B) (linear, bilinear; loaded models at their full width
+        N (nw + 1)) or of Kf (nonlinear); trials: a list of (zeta0 (nzeta), U (T x m), Yreal (T x n), Wl (T x nw) or None),
+        the rows after the nd shift; yfactor (n): the factors of scaleup.y.  Returns (err (nmod, ntr, 3 n + 2):
+        [mean | rmse | nrmse | euclid_mean | unscaled euclid_mean], status (nmod, ntr): 1 where the simulated outputs left
+        the finite range, sim: a list per model of a list per trial of T x n arrays, or None)."""
+        N, m, nz, n, nw = basis.N, basis.m, basis.nzeta, int(n), int(nw)
+        nmod, ntr = len(models), len(trials)
+        A, B, off, z0, U, Y, W = self._validate_pack(basis, model_type, models, trials, n, nw)
+        rows = int(off[-1])
         fac = np.ascontiguousarray(np.broadcast_to(np.asarray(yfactor, dtype=np.float64), (n,)))
         err = np.zeros((nmod, ntr, 3 * n + 2)); st = np.zeros((nmod, ntr), dtype=np.int32)
         S = np.zeros((nmod, n, rows)) if want_sim else None
@@ -417,6 +424,31 @@ class Context:
         if want_sim:
             sim = [[np.ascontiguousarray(S[i, :, off[q]:off[q + 1]].T) for q in range(ntr)] for i in range(nmod)]
         return err, st, sim
+
+    def validate_ct(self, basis, model_type, models, trials, n, yfactor, Ts, rtol=1e-3, atol=1e-6, want_sim=False, nw=0):
+        """kp_validate_ct: `validate` for continuous-time models - every sample interval of every (model, trial) pair is ode45
+        over [0, Ts] with the input held (the step control of rollout_ct / rollout_nl_ct), one launch for the whole table.
+        models and trials as `validate` takes them (no loads: the fourth entry of a trial is ignored, and nw other than 0 is
+        refused by the library).  Returns (err, status, sim, naccept, nreject): err, status and sim as `validate`, status 1
+        also where the integration failed (the samples from the failing one on are NaN); naccept, nreject (nmod, ntr): the
+        accepted / rejected steps of each pair."""
+        N, m, nz, n, nw = basis.N, basis.m, basis.nzeta, int(n), int(nw)
+        nmod, ntr = len(models), len(trials)
+        A, B, off, z0, U, Y, _ = self._validate_pack(basis, model_type, models, trials, n, 0)
+        rows = int(off[-1])
+        fac = np.ascontiguousarray(np.broadcast_to(np.asarray(yfactor, dtype=np.float64), (n,)))
+        err = np.zeros((nmod, ntr, 3 * n + 2)); st = np.zeros((nmod, ntr), dtype=np.int32)
+        na = np.zeros((nmod, ntr), dtype=np.int32); nr = np.zeros((nmod, ntr), dtype=np.int32)
+        S = np.zeros((nmod, n, rows)) if want_sim else None
+        F.check(F.lib().kp_validate_ct(self._h, basis.handle, F.MODEL[model_type], N, m, n, nz, nw, nmod, F.dptr(A), F.dptr(B), ntr,
+                                       off.ctypes.data_as(C.POINTER(C.c_int64)), F.dptr(z0), F.dptr(U), F.dptr(Y), None,
+                                       F.dptr(fac), int(bool(want_sim)), float(Ts), float(rtol), float(atol), F.dptr(err),
+                                       st.ctypes.data_as(F.c_ip), F.dptr(S), na.ctypes.data_as(F.c_ip), nr.ctypes.data_as(F.c_ip)),
+                self._h)
+        sim = None
+        if want_sim:
+            sim = [[np.ascontiguousarray(S[i, :, off[q]:off[q + 1]].T) for q in range(ntr)] for i in range(nmod)]
+        return err, st, sim, na, nr
 
     def qp_solve(self, H, f, A, b):
         """quadprog_gurobi(H,f,A,b) shim: NaN vector on failure (quadprog_gurobi.m:22-23)."""

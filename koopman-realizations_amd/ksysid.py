@@ -787,7 +787,7 @@ class Ksysid:
         return {"nonlinear": self.val_NLmodel, "bilinear": self.val_BLmodel, "linear": self.val_model}[self.model_type](model, valdata)
 
     def _val_table_loop(self, models, trials, want_sim):
-        """The table by one val_* call per (model, trial): continuous time, and shapes kp_validate refuses."""
+        """The table by one val_* call per (model, trial): the shapes kp_validate / kp_validate_ct refuse."""
         n = self.params["n"]
         nmod, ntr = len(models), len(trials)
         tab = {k: np.zeros((nmod, ntr, n)) for k in ("mean", "rmse", "nrmse")}
@@ -810,13 +810,14 @@ class Ksysid:
     def val_candidates(self, models=None, valdata=None, want_sim=False):
         """The validation table of valNplot_model (Ksysid.m:1928-1972) run for every candidate: each model rolled out over
         each validation trial and the errors of get_error (:1886-1897), in ONE device call (kp_validate: models and trials
-        uploaded once, one launch for the nmod x ntr rollouts with the load of every step, errors reduced in the kernel).
+        uploaded once, one launch for the nmod x ntr rollouts with the load of every step, errors reduced in the kernel;
+        time_type = 'continuous': kp_validate_ct, the same with ode45 over every sample interval at ode_rtol / ode_atol).
         models: a model dict or a list of them (default: self.candidates, else [self.model]); valdata: a trial or a list
         (default self.valdata; scaled, as val_model takes them).  Returns a dict of arrays: mean, rmse, nrmse
         (nmod x ntr x n), euclid_mean, unscaled_euclid_mean (nmod x ntr), diverged (bool: the simulated outputs left the
         finite range; the errors are then Inf / NaN, as MATLAB gives silently), lasso (nmod) when every model carries it,
-        and with want_sim sim[i][q]: the T_q x n simulated outputs.  Continuous-time models, and shapes the kernel refuses
-        (its LDS limits), go through the per-trial val_model / val_BLmodel / val_NLmodel loop and fill the same dict."""
+        and with want_sim sim[i][q]: the T_q x n simulated outputs.  Shapes the kernel refuses (its LDS limits) go through
+        the per-trial val_model / val_BLmodel / val_NLmodel loop and fill the same dict."""
         if models is None:
             models = self.candidates if self.candidates is not None else self.model
         if models is None:
@@ -827,26 +828,29 @@ class Ksysid:
         trials = [valdata] if isinstance(valdata, dict) else list(valdata)
         if not models or not trials:
             raise ValueError("val_candidates needs at least one model and one trial")
+        p = self.params; n, nw = p["n"], p["nw"]
+        packed = []
+        for v in trials:
+            _, yreal, ureal, zetareal = self._val_common(v)
+            w = np.asarray(v["w"], dtype=np.float64).reshape(len(np.ravel(v["t"])), -1)[p["nd"]:] if self.loaded else None
+            packed.append((zetareal[0], ureal, yreal, w))
+        mods = [mo["Kf"] for mo in models] if self.model_type == "nonlinear" else [(mo["A"], mo["B"]) for mo in models]
         tab = None
-        if self.time_type != "continuous":
-            p = self.params; n, nw = p["n"], p["nw"]
-            packed = []
-            for v in trials:
-                _, yreal, ureal, zetareal = self._val_common(v)
-                w = np.asarray(v["w"], dtype=np.float64).reshape(len(np.ravel(v["t"])), -1)[p["nd"]:] if self.loaded else None
-                packed.append((zetareal[0], ureal, yreal, w))
-            mods = [mo["Kf"] for mo in models] if self.model_type == "nonlinear" else [(mo["A"], mo["B"]) for mo in models]
-            try:
-                err, st, sim = self.ctx.validate(self.basis_dev, self.model_type, mods, packed, n, nw, p["scale"]["y_factor"], want_sim)
-            except F.KoopmanHipError as e:
-                if e.code != F.KP_ERR_ARG:
-                    raise
+        try:
+            if self.time_type == "continuous":
+                err, st, sim = self.ctx.validate_ct(self.basis_dev, self.model_type, mods, packed, n, p["scale"]["y_factor"], p["Ts"],
+                                                    self.ode_rtol, self.ode_atol, want_sim)[:3]
             else:
-                tab = {"mean": err[:, :, :n].copy(), "rmse": err[:, :, n:2 * n].copy(), "nrmse": err[:, :, 2 * n:3 * n].copy(),
-                       "euclid_mean": err[:, :, 3 * n].copy(), "unscaled_euclid_mean": err[:, :, 3 * n + 1].copy(),
-                       "diverged": st != 0}
-                if want_sim:
-                    tab["sim"] = sim
+                err, st, sim = self.ctx.validate(self.basis_dev, self.model_type, mods, packed, n, nw, p["scale"]["y_factor"], want_sim)
+        except F.KoopmanHipError as e:
+            if e.code != F.KP_ERR_ARG:
+                raise
+        else:
+            tab = {"mean": err[:, :, :n].copy(), "rmse": err[:, :, n:2 * n].copy(), "nrmse": err[:, :, 2 * n:3 * n].copy(),
+                   "euclid_mean": err[:, :, 3 * n].copy(), "unscaled_euclid_mean": err[:, :, 3 * n + 1].copy(),
+                   "diverged": st != 0}
+            if want_sim:
+                tab["sim"] = sim
         if tab is None:
             tab = self._val_table_loop(models, trials, want_sim)
         if all("lasso" in mo for mo in models):

@@ -9,7 +9,11 @@ of its ten training trials (1201 rows each) are held out as the other four; the 
 snapshot counts (what is timed does not depend on how a candidate was fitted).
 Then the toy loaded system (tests/_loaded_system.py, nw = 2) with a load that changes at every step - a random walk inside
 [-1, 1] - where the per-trial route launches once per sample: one model on the two validation trials of 150 rows.
-Prints one JSON line per configuration, and the largest difference between the two routes' euclid_mean."""
+Then the same arm shape with time_type = 'continuous' (kp_validate_ct against the loop of kp_rollout_ct / kp_rollout_nl_ct
+calls, ode45 over every sample interval): the 16 candidates are the trained continuous model with its matrix scaled by
+1 + i / 1000, since the matrix logarithm of a fit on a subset of the pairs need not exist.
+Prints one JSON line per configuration, and the largest difference between the two routes' euclid_mean.
+Usage: validate_time.py [all | discrete | continuous]."""
 import json
 import os
 import sys
@@ -57,20 +61,33 @@ def compare(ks, cands, trials, label):
                       "ratio": round(t_loop / t_one, 1), "diverged": int(tab["diverged"].sum()), "max_diff_euclid_mean": diff}), flush=True)
 
 
+def scaled_candidates(ks, count):
+    key = "Kf" if ks.model_type == "nonlinear" else "A"
+    return [dict(ks.model, **{key: np.asfortranarray(ks.model[key] * (1.0 + 1e-3 * i))}) for i in range(count)]
+
+
 def main():
+    which = sys.argv[1] if len(sys.argv) > 1 else "all"
+    if which not in ("all", "discrete", "continuous"):
+        raise SystemExit(__doc__)
     g = np.load(os.path.join(ROOT, "tests", "golden", "arm_data.npz"))
     off = np.concatenate([[0], np.cumsum(g["train_len"])])
     runs = [{"t": g["train_t"][a:b], "y": g["train_y"][a:b], "u": g["train_u"][a:b]} for a, b in zip(off[:-1], off[1:])]
     val = [{"t": g["val_t"], "y": g["val_y"], "u": g["val_u"]}] + runs[6:]
     ctx = kra.Context(0)
-    for mt in ("linear", "bilinear", "nonlinear"):
+    for mt in ("linear", "bilinear", "nonlinear") if which != "continuous" else ():
         ks = kra.Ksysid({"train": runs[:6], "val": val}, ctx=ctx, model_type=mt, obs_type=["poly"], obs_degree=[3], dim_red=True)
         npairs = len(ks.snapshotPairs["alpha"])
         cands = candidates(ks, np.linspace(npairs // 2, npairs, 16).astype(int))
         compare(ks, cands, ks.valdata, "arm 16 x 5")
+    for mt in ("linear", "bilinear", "nonlinear") if which != "discrete" else ():
+        ks = kra.Ksysid({"train": runs[:6], "val": val}, ctx=ctx, model_type=mt, obs_type=["poly"], obs_degree=[3], dim_red=True,
+                        time_type="continuous")
+        ks.train_models()
+        compare(ks, scaled_candidates(ks, 16), ks.valdata, "arm 16 x 5, continuous")
     rng = np.random.default_rng(3)
     trials = make_trials(10, 150, nw=2, seed=21)
-    for mt in ("linear", "bilinear", "nonlinear"):
+    for mt in ("linear", "bilinear", "nonlinear") if which != "continuous" else ():
         ks = kra.Ksysid({"train": trials[:8], "val": trials[8:]}, ctx=ctx, model_type=mt, obs_type=["poly"], obs_degree=[2], loaded=True)
         ks.train_models()
         walk = []
