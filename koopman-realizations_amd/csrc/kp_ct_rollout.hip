@@ -1,14 +1,11 @@
 // Continuous-time validation rollouts (koopman_hip_ct.h): every sample interval of val_model / val_BLmodel / val_NLmodel
 // (Ksysid.m:1679-1683, 1777-1781, 1849-1856) is ode45 over [0, Ts] with the input held, from the end point of the previous one.
-// The integrator restates ode45's Dormand-Prince 5(4) pair and step control exactly as arm.dopri45 does (initial step, MaxStep
-// Ts / 10, the 1.1 h stretch to the end point, first-failure shrink then halving, growth of at most 5x).
+// The integrator is kp_ct_step.h's workgroup-wide ode45 (right-hand side, per-sample model, step control), which
+// kp_validate_ct.hip runs as well; this file keeps the LDS layout, the staging of the model and the inputs, and the outputs.
 //
 // One workgroup per rollout.  The steps are serial, so everything a stage touches lives in LDS: the state, the seven stages,
 // the inputs of a chunk of samples and, when it fits, the model (for a bilinear model the matrix A + sum_i u_i B_i of the
-// sample, formed once per sample; in global memory beyond 90 states, where B streams from L2).  Thread r owns rows r, r + nth,
-// ... of every vector, so a stage needs one barrier (its input complete) before the right-hand side; stage inputs alternate
-// between two buffers.  The error norm is one workgroup max per step.  Every thread runs the same step control on the same
-// LDS values, so control flow stays uniform.
+// sample, formed once per sample; in global memory beyond 90 states, where B streams from L2).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,83 +40,47 @@ __global__ __launch_bounds__(256) void kp_ct_rollout_kernel(CtArgs g, BasisDev b
   extern __shared__ double sm[];
   const int tid = threadIdx.x, nth = blockDim.x, bi = blockIdx.x;
   const int NS = g.NS, N = g.N, m = g.m, T = g.T;
-  double* y = sm;
-  double* yn = y + NS;
-  double* yt0 = yn + NS;                      // matrix models: two stage-input buffers
-  double* yt1 = yt0 + NS;
-  double* kk = yt1 + NS;                      // 7 x NS
-  double* red = kk + 7 * NS;                  // 16
-  double* Uc = red + 16;                      // m x tc
+  CtStep w;
+  w.N = N; w.m = m; w.NS = NS; w.kind = g.kind;
+  w.y = sm;
+  w.yn = w.y + NS;
+  w.yt0 = w.yn + NS;                          // matrix models: two stage-input buffers
+  w.yt1 = w.yt0 + NS;
+  w.kk = w.yt1 + NS;                          // 7 x NS
+  w.red = w.kk + 7 * NS;                      // 16
+  double* Uc = w.red + 16;                    // m x tc
   double* extra = Uc + (size_t)m * g.tc;
   // matrix models: bu (N) then the staged matrix; nonlinear: v (nvars), full (nfull), zl (N), staged Kf
-  double* bu = extra;
-  double* Ash = bu + N;
-  double* v = extra;
-  double* full = NL ? v + bd.nvars : nullptr;
-  double* zl = NL ? full + bd.nfull : nullptr;
-  double* Ksh = NL ? zl + N : nullptr;
+  w.bu = extra;
+  double* Ash = w.bu + N;
+  w.v = extra;
+  w.full = NL ? w.v + bd.nvars : nullptr;
+  w.zl = NL ? w.full + bd.nfull : nullptr;
+  double* Ksh = NL ? w.zl + N : nullptr;
   const double* Ab = g.A + (size_t)bi * (NL ? (size_t)NS * N : (size_t)N * N);
-  const double* Bb = NL ? nullptr : g.B + (size_t)bi * N * (g.kind == 1 ? (size_t)N * m : (size_t)m);
+  w.Ab = Ab;
+  w.Bb = NL ? nullptr : g.B + (size_t)bi * N * (g.kind == 1 ? (size_t)N * m : (size_t)m);
   const double* Ub = g.U + (size_t)bi * T * m;
   double* Yb = g.Y + (size_t)bi * T * g.n_out;
-  const double* Am = Ab;                      // the matrix of the right-hand side (linear: A, bilinear: A + sum u_i B_i)
+  w.Am = Ab;
   if (!NL) {
-    if (g.kind == 1) Am = g.stageA ? Ash : g.Ag + (size_t)bi * N * N;
+    if (g.kind == 1) w.Am = g.stageA ? Ash : g.Ag + (size_t)bi * N * N;
     else if (g.stageA) {
       for (int e = tid; e < N * N; e += nth) Ash[e] = Ab[e];
-      Am = Ash;
+      w.Am = Ash;
     }
   } else if (g.stageA) {
     for (int e = tid; e < NS * N; e += nth) Ksh[e] = Ab[e];
-    Am = Ksh;
+    w.Am = Ksh;
   }
-  for (int r = tid; r < NS; r += nth) y[r] = g.z0[(size_t)bi * NS + r];
-  int flip = 0, failed = 0, nacc = 0, nrej = 0;
-  const double rtol = g.rtol, thr = g.atol / g.rtol, Ts = g.Ts, hmax = 0.1 * fabs(Ts);
-  const double* uc = Uc;     // inputs of the current sample: uc[i * tc]
-
-  // right-hand side f(x) -> out (own rows).  Matrix models: x complete (the caller's barrier).  Nonlinear: x is v[0..nz)
-  // (own rows written by the caller), the lift runs inside behind its own barriers.
-  auto rhs = [&](const double* x, double* out) {
-    if (!NL) {
-      for (int r = tid; r < N; r += nth) {
-        double s = 0.0;
-#pragma unroll 4
-        for (int c = 0; c < N; ++c) s += Am[r + (size_t)c * N] * x[c];
-        out[r] = g.kind == 0 ? s + bu[r] : s;
-      }
-    } else {
-      __syncthreads();
-      for (int c = tid; c < bd.nfull; c += nth) full[c] = kp_eval_col(bd, bd.cols[c], v, 1);
-      __syncthreads();
-      const double* z = full;
-      if (bd.k_pcs) {
-        for (int c = tid; c < N; c += nth) {
-          double val;
-          if (c < bd.nvars) val = v[c];
-          else if (c < bd.nvars + bd.k_pcs) {
-            const double* pc = bd.pcs + (size_t)(c - bd.nvars) * bd.nfull;
-            val = 0.0;
-            for (int i = 0; i < bd.nfull; ++i) val += pc[i] * full[i];
-          } else val = 1.0;
-          zl[c] = val;
-        }
-        __syncthreads();
-        z = zl;
-      }
-      for (int r = tid; r < NS; r += nth) {
-        double s = 0.0;
-        for (int c = 0; c < N; ++c) s += Am[r + (size_t)c * NS] * z[c];
-        out[r] = s;
-      }
-    }
-  };
+  for (int r = tid; r < NS; r += nth) w.y[r] = g.z0[(size_t)bi * NS + r];
+  w.rtol = g.rtol; w.thr = g.atol / g.rtol; w.Ts = g.Ts; w.hmax = 0.1 * fabs(g.Ts);
 
   for (int j = 0; j < T; ++j) {
-    for (int r = tid; r < g.n_out; r += nth) Yb[(size_t)r * T + j] = y[r];
+    for (int r = tid; r < g.n_out; r += nth) Yb[(size_t)r * T + j] = w.y[r];
     if (j == T - 1) break;
-    if (failed) {
-      for (int r = tid; r < NS; r += nth) y[r] = NAN;
+    if (w.failed) {
+      for (int r = tid; r < NS; r += nth) w.y[r] = NAN;
       continue;
     }
     const int jc = j % g.tc;
@@ -131,114 +92,14 @@ __global__ __launch_bounds__(256) void kp_ct_rollout_kernel(CtArgs g, BasisDev b
       }
       __syncthreads();
     }
-    uc = Uc + jc;
-    // per-sample model: linear B u, bilinear A + sum_i u_i B_i, nonlinear [zeta; u]
-    if (!NL) {
-      if (g.kind == 0) {
-        for (int r = tid; r < N; r += nth) {
-          double s = 0.0;
-          for (int i = 0; i < m; ++i) s += Bb[r + (size_t)i * N] * uc[i * g.tc];
-          bu[r] = s;
-        }
-      } else {
-        double* Aw = const_cast<double*>(Am);
-        for (int e = tid; e < N * N; e += nth) {
-          double s = Ab[e];
-          for (int i = 0; i < m; ++i) s += uc[i * g.tc] * Bb[(size_t)i * N * N + e];
-          Aw[e] = s;
-        }
-      }
-    } else {
-      for (int i = tid; i < m; i += nth) v[NS + i] = uc[i * g.tc];
-      for (int r = tid; r < NS; r += nth) v[r] = y[r];
-    }
+    ct_sample_model<NL>(w, Uc + jc, g.tc);     // inputs of the sample: Uc[jc + i * tc]
     __syncthreads();
-    // ---- dopri45 over [0, Ts] from y ----
-    double* k0 = kk;
-    double* k6 = kk + 6 * NS;
-    rhs(y, k0);
-    double loc = 0.0;
-    for (int r = tid; r < NS; r += nth) loc = ct_max(loc, fabs(k0[r] / fmax(fabs(y[r]), thr)));
-    double rh = ct_block_max(loc, red, flip) / (0.8 * pow(rtol, 0.2));
-    double t = 0.0;
-    double h = fmin(hmax, fabs(Ts));
-    if (h * rh > 1.0) h = 1.0 / rh;
-    h = fmax(h, 16.0 * CT_EPS * 1e-300);
-    int attempts = 0;
-    while (t < Ts && !failed) {
-      const double hmin = 16.0 * CT_EPS * fmax(fabs(t), 1e-300);
-      h = fmin(hmax, fmax(hmin, h));
-      if (1.1 * h >= Ts - t) h = Ts - t;
-      bool nofail = true;
-      double err, tnew;
-      for (;;) {
-        for (int s = 1; s < 6; ++s) {
-          double* xin = NL ? v : ((s & 1) ? yt1 : yt0);
-          for (int r = tid; r < NS; r += nth) {
-            double acc = 0.0;
-            for (int q = 0; q < s; ++q) acc += dp_a(s, q) * kk[q * NS + r];
-            xin[r] = y[r] + h * acc;
-          }
-          if (!NL) __syncthreads();
-          rhs(xin, kk + s * NS);
-        }
-        for (int r = tid; r < NS; r += nth) {
-          double acc = 0.0;
-          for (int q = 0; q < 6; ++q) acc += dp_a(6, q) * kk[q * NS + r];
-          yn[r] = y[r] + h * acc;
-          if (NL) v[r] = yn[r];
-        }
-        tnew = t + h;
-        if (!NL) __syncthreads();
-        rhs(yn, k6);
-        double le = 0.0;
-        for (int r = tid; r < NS; r += nth) {
-          double e = 0.0;
-          for (int q = 0; q < 7; ++q) e += dp_e(q) * kk[q * NS + r];
-          le = ct_max(le, fabs(e) / fmax(fmax(fabs(y[r]), fabs(yn[r])), thr));
-          if (!(fabs(yn[r]) < INFINITY)) le = NAN;
-        }
-        err = h * ct_block_max(le, red, flip);
-        ++attempts;
-        if (!(err < INFINITY) || attempts > CT_MAX_ATTEMPTS) { failed = 1; break; }
-        if (err > rtol) {
-          if (h <= hmin) { failed = 1; break; }     // step-size underflow
-          ++nrej;
-          if (nofail) {
-            nofail = false;
-            h = fmax(hmin, h * fmax(0.1, 0.8 * pow(rtol / err, 0.2)));
-          } else {
-            h = fmax(hmin, 0.5 * h);
-          }
-          continue;
-        }
-        break;
-      }
-      if (failed) break;
-      double hnext;
-      if (nofail) {
-        const double temp = 1.25 * pow(err / rtol, 0.2);
-        hnext = temp > 0.2 ? h / temp : 5.0 * h;
-      } else {
-        hnext = h;
-      }
-      t = tnew;
-      ++nacc;
-      { double* tmp = y; y = yn; yn = tmp; }
-      // FSAL: the last stage of the accepted step is the first of the next
-      double* kl = kk + 6 * NS;
-      for (int r = tid; r < NS; r += nth) kk[r] = kl[r];
-      if (NL) for (int r = tid; r < NS; r += nth) v[r] = y[r];
-      h = hnext;
-    }
-    if (failed)
-      for (int r = tid; r < NS; r += nth) y[r] = NAN;
-    __syncthreads();     // y complete before the next sample's model and right-hand side read it
+    ct_integrate<NL>(w, bd);
   }
   if (tid == 0) {
-    if (g.nacc) g.nacc[bi] = nacc;
-    if (g.nrej) g.nrej[bi] = nrej;
-    g.status[bi] = failed ? KP_ERR_NOT_CONVERGED : KP_OK;
+    if (g.nacc) g.nacc[bi] = w.nacc;
+    if (g.nrej) g.nrej[bi] = w.nrej;
+    g.status[bi] = w.failed ? KP_ERR_NOT_CONVERGED : KP_OK;
   }
 }
 
@@ -295,10 +156,6 @@ int ct_launch(kp_ctx* ctx, const char* fn, bool nl, CtArgs g, const BasisDev* bd
   (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
   ctx->timers[5] = ms;
   return KP_OK;
-}
-
-bool ct_tol_ok(double Ts, double rtol, double atol) {
-  return std::isfinite(Ts) && Ts > 0 && std::isfinite(rtol) && rtol > 0 && std::isfinite(atol) && atol > 0;
 }
 
 }  // namespace

@@ -18,12 +18,15 @@
 // Order of the reductions, fixed in time: behind the recurrence of a chunk, thread tt forms the two Euclidean norms of step tt
 // (sum over the outputs in ascending order); then thread c < n adds |d|, d^2 and min / max of yreal of column c over the steps
 // of the chunk in ascending order, thread n and n + 1 the two norms likewise, each into its accumulator, which runs on from
-// chunk to chunk.  No atomics, no tree: the sums are those of a serial loop over t.
+// chunk to chunk.  No atomics, no tree: the sums are those of a serial loop over t.  kp_validate_ct.hip restates these
+// statements with its own barrier and chunk length, on purpose: a change to one reduction must be made in the other.  The
+// argument checks are kp_validate_args.h's, shared with kp_validate_ct.
 #include <algorithm>
 #include <cmath>
 
 #include "kp_internal.h"
 #include "koopman_hip_validate.h"
+#include "kp_validate_args.h"
 
 #define VAL_TC KP_VALIDATE_CHUNK
 #define VAL_TCP (VAL_TC + 1)   // row stride of Yr / Ys: thread c walks row c in the column reduction
@@ -256,33 +259,12 @@ extern "C" int kp_validate(kp_ctx* ctx, const kp_basis* basis, int model_type, i
                            const double* Yreal, const double* Wl, const double* yfactor, int want_sim, double* err_out,
                            int* status_out, double* Ysim) {
   if (!ctx) return KP_ERR_ARG;
-  if (!basis || !A || !trial_off || !zeta0 || !Yreal || !yfactor || !err_out || !status_out || nmod < 1 || ntr < 1 || N < 1 || m < 0 ||
-      n < 1 || nzeta < 1 || nw < 0)
-    return ctx->fail(KP_ERR_ARG, "kp_validate: bad argument");
-  if (model_type != KP_MODEL_LINEAR && model_type != KP_MODEL_BILINEAR && model_type != KP_MODEL_NONLINEAR)
-    return ctx->fail(KP_ERR_ARG, "kp_validate: unknown model type");
+  const int rc_arg = val_check_args(ctx, "kp_validate", basis, model_type, N, m, n, nzeta, nw, nmod, A, B, ntr, trial_off, zeta0, U,
+                                    Yreal, yfactor, want_sim, err_out, status_out, Ysim);
+  if (rc_arg) return rc_arg;
+  if (nw > 0 && !Wl) return ctx->fail(KP_ERR_ARG, "kp_validate: Wl required for a loaded model");
   const bool nl = model_type == KP_MODEL_NONLINEAR, bil = model_type == KP_MODEL_BILINEAR;
   const BasisDev& b = basis->dev;
-  if (b.model_type != model_type)
-    return ctx->fail(KP_ERR_ARG, "kp_validate: the dictionary is of model type " + std::to_string(b.model_type) + ", the models of type " +
-                                     std::to_string(model_type));
-  if (b.N != N || b.m != m || b.nzeta != nzeta)
-    return ctx->fail(KP_ERR_ARG, "kp_validate: N, m and nzeta must be those of the dictionary (" + std::to_string(b.N) + ", " +
-                                     std::to_string(b.m) + ", " + std::to_string(b.nzeta) + ")");
-  if (n > N || (nl && n > nzeta))
-    return ctx->fail(KP_ERR_ARG, "kp_validate: n = " + std::to_string(n) + " outputs, but the state has " + std::to_string(nl ? nzeta : N) +
-                                     " entries");
-  if (!nl && !B) return ctx->fail(KP_ERR_ARG, "kp_validate: B required");
-  if (m > 0 && !U) return ctx->fail(KP_ERR_ARG, "kp_validate: U required");
-  if (nw > 0 && !Wl) return ctx->fail(KP_ERR_ARG, "kp_validate: Wl required for a loaded model");
-  if (want_sim && !Ysim) return ctx->fail(KP_ERR_ARG, "kp_validate: Ysim required with want_sim");
-  if (trial_off[0] != 0) return ctx->fail(KP_ERR_ARG, "kp_validate: trial_off must start at 0");
-  for (int q = 0; q < ntr; ++q) {
-    const int64_t Tq = trial_off[q + 1] - trial_off[q];
-    if (Tq < 1) return ctx->fail(KP_ERR_ARG, "kp_validate: trial " + std::to_string(q) + " is empty");
-    if (Tq > INT32_MAX) return ctx->fail(KP_ERR_ARG, "kp_validate: trial " + std::to_string(q) + " is too long");
-  }
-  if ((int64_t)nmod * ntr > INT32_MAX) return ctx->fail(KP_ERR_ARG, "kp_validate: too many (model, trial) pairs");
   const int64_t rows = trial_off[ntr];
   const size_t NL = (size_t)N * (nw + 1);
   if (NL > (size_t)INT32_MAX / (size_t)std::max(1, m + 1)) return ctx->fail(KP_ERR_ARG, "kp_validate: model too wide");

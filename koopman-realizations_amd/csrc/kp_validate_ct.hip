@@ -5,9 +5,9 @@
 // reduction of kp_validate.hip, and replaces nmod x ntr calls of kp_rollout_ct / kp_rollout_nl_ct of one workgroup each.
 //
 // One workgroup per (model, trial) pair, nothing shared between pairs but the read-only models: the numbers of a pair are the
-// same bits alone or in a batch.  Thread r owns rows r, r + nth, ... of every vector, so a stage needs one barrier (its input
-// complete) before the right-hand side; every thread runs the same step control on the same LDS values.  The step control is
-// that of kp_ct_rollout_kernel, statement for statement.
+// same bits alone or in a batch.  The right-hand side, the per-sample model and the integration of a sample interval are
+// kp_ct_step.h's, the code kp_ct_rollout_kernel runs, and the argument checks are kp_validate_args.h's, shared with
+// kp_validate.hip.  This file keeps the grid, the LDS layout, the staging of the model and of a chunk, and the error reduction.
 //   - A linear A or a nonlinear Kf of at most KP_VALIDATE_CT_STAGE doubles is staged in LDS, a larger one is read from memory
 //     (L2; the models are uploaded once per call, nmod of them).  The bilinear matrix of a sample, A + sum_i u_i B_i, is private
 //     to the pair: in LDS under the same limit, else in the pair's slice of a scratch buffer.
@@ -20,13 +20,15 @@
 //
 // Order of the reductions: that of kp_validate_kernel - behind the rollout of a chunk, thread tt forms the two Euclidean norms
 // of sample tt, then thread c < n adds |d|, d^2 and min / max of yreal of column c over the chunk in ascending time, thread n
-// and n + 1 the two norms likewise.  No atomics, no tree.
+// and n + 1 the two norms likewise.  No atomics, no tree.  The statements are restated from kp_validate.hip on purpose: the
+// two kernels differ in their barrier and chunk length, and a change to one reduction must be made in the other.
 #include <algorithm>
 #include <cmath>
 
 #include "koopman_hip_validate.h"
 #include "kp_ct_step.h"
 #include "kp_internal.h"
+#include "kp_validate_args.h"
 
 namespace {
 
@@ -61,13 +63,15 @@ __global__ __launch_bounds__(256) void kp_validate_ct_kernel(VctArgs g, BasisDev
   const int NS = g.NS, N = g.N, m = g.m, n = g.n;
   const int64_t r0 = g.off[tr];
   const int T = (int)(g.off[tr + 1] - r0);
-  double* y = sm;
-  double* yn = y + NS;
-  double* yt0 = yn + NS;                      // matrix models: two stage-input buffers
-  double* yt1 = yt0 + NS;
-  double* kk = yt1 + NS;                      // 7 x NS
-  double* red = kk + 7 * NS;                  // 16
-  double* acc = red + 16;                     // [c][sum |d|, sum d^2, min, max] | euclid | unscaled euclid | not finite
+  CtStep w;
+  w.N = N; w.m = m; w.NS = NS; w.kind = g.kind;
+  w.y = sm;
+  w.yn = w.y + NS;
+  w.yt0 = w.yn + NS;                          // matrix models: two stage-input buffers
+  w.yt1 = w.yt0 + NS;
+  w.kk = w.yt1 + NS;                          // 7 x NS
+  w.red = w.kk + 7 * NS;                      // 16
+  double* acc = w.red + 16;                   // [c][sum |d|, sum d^2, min, max] | euclid | unscaled euclid | not finite
   double* fs = acc + 4 * n + 4;
   double* Uc = fs + n;
   double* Yr = Uc + m * VCT_TC;
@@ -75,24 +79,25 @@ __global__ __launch_bounds__(256) void kp_validate_ct_kernel(VctArgs g, BasisDev
   double* Ec = Ys + n * VCT_TCP;
   double* Euc = Ec + VCT_TC;
   double* extra = Euc + VCT_TC;
-  double* bu = extra;
-  double* Ash = bu + N;
-  double* v = extra;
-  double* full = NL ? v + bd.nvars : nullptr;
-  double* zl = NL ? full + bd.nfull : nullptr;
-  double* Ksh = NL ? zl + N : nullptr;
+  w.bu = extra;
+  double* Ash = w.bu + N;
+  w.v = extra;
+  w.full = NL ? w.v + bd.nvars : nullptr;
+  w.zl = NL ? w.full + bd.nfull : nullptr;
+  double* Ksh = NL ? w.zl + N : nullptr;
   const double* Ab = g.A + (size_t)mod * (NL ? (size_t)NS * N : (size_t)N * N);
-  const double* Bb = NL ? nullptr : g.B + (size_t)mod * N * (g.kind == 1 ? (size_t)N * m : (size_t)m);
-  const double* Am = Ab;                      // the matrix of the right-hand side (linear: A, bilinear: A + sum u_i B_i)
+  w.Ab = Ab;
+  w.Bb = NL ? nullptr : g.B + (size_t)mod * N * (g.kind == 1 ? (size_t)N * m : (size_t)m);
+  w.Am = Ab;
   if (!NL) {
-    if (g.kind == 1) Am = g.stage ? Ash : g.Ag + (size_t)blockIdx.x * N * N;
+    if (g.kind == 1) w.Am = g.stage ? Ash : g.Ag + (size_t)blockIdx.x * N * N;
     else if (g.stage) {
       for (int e = tid; e < N * N; e += nth) Ash[e] = Ab[e];
-      Am = Ash;
+      w.Am = Ash;
     }
   } else if (g.stage) {
     for (int e = tid; e < NS * N; e += nth) Ksh[e] = Ab[e];
-    Am = Ksh;
+    w.Am = Ksh;
   }
   for (int c = tid; c < n; c += nth) {
     acc[4 * c] = 0.0;
@@ -102,46 +107,8 @@ __global__ __launch_bounds__(256) void kp_validate_ct_kernel(VctArgs g, BasisDev
     fs[c] = g.yfac[c];
   }
   if (tid < 3) acc[4 * n + tid] = 0.0;
-  for (int r = tid; r < NS; r += nth) y[r] = g.Z0[tr + (size_t)r * g.ntr];
-  int flip = 0, failed = 0, nacc = 0, nrej = 0;
-  const double rtol = g.rtol, thr = g.atol / g.rtol, Ts = g.Ts, hmax = 0.1 * fabs(Ts);
-
-  // right-hand side f(x) -> out (own rows).  Matrix models: x complete (the caller's barrier).  Nonlinear: x is v[0..nz)
-  // (own rows written by the caller), the lift runs inside behind its own barriers.
-  auto rhs = [&](const double* x, double* out) {
-    if (!NL) {
-      for (int r = tid; r < N; r += nth) {
-        double s = 0.0;
-#pragma unroll 4
-        for (int c = 0; c < N; ++c) s += Am[r + (size_t)c * N] * x[c];
-        out[r] = g.kind == 0 ? s + bu[r] : s;
-      }
-    } else {
-      __syncthreads();
-      for (int c = tid; c < bd.nfull; c += nth) full[c] = kp_eval_col(bd, bd.cols[c], v, 1);
-      __syncthreads();
-      const double* z = full;
-      if (bd.k_pcs) {
-        for (int c = tid; c < N; c += nth) {
-          double val;
-          if (c < bd.nvars) val = v[c];
-          else if (c < bd.nvars + bd.k_pcs) {
-            const double* pc = bd.pcs + (size_t)(c - bd.nvars) * bd.nfull;
-            val = 0.0;
-            for (int i = 0; i < bd.nfull; ++i) val += pc[i] * full[i];
-          } else val = 1.0;
-          zl[c] = val;
-        }
-        __syncthreads();
-        z = zl;
-      }
-      for (int r = tid; r < NS; r += nth) {
-        double s = 0.0;
-        for (int c = 0; c < N; ++c) s += Am[r + (size_t)c * NS] * z[c];
-        out[r] = s;
-      }
-    }
-  };
+  for (int r = tid; r < NS; r += nth) w.y[r] = g.Z0[tr + (size_t)r * g.ntr];
+  w.rtol = g.rtol; w.thr = g.atol / g.rtol; w.Ts = g.Ts; w.hmax = 0.1 * fabs(g.Ts);
 
   double* Yo = g.want_sim ? g.Ysim + (size_t)mod * g.rows * n : nullptr;
   for (int t0 = 0; t0 < T; t0 += VCT_TC) {
@@ -158,115 +125,15 @@ __global__ __launch_bounds__(256) void kp_validate_ct_kernel(VctArgs g, BasisDev
     __syncthreads();
     for (int tt = 0; tt < tc; ++tt) {
       const int j = t0 + tt;
-      for (int r = tid; r < n; r += nth) Ys[r * VCT_TCP + tt] = j == 0 ? Yr[r * VCT_TCP] : y[r];   // row 0: :1654
+      for (int r = tid; r < n; r += nth) Ys[r * VCT_TCP + tt] = j == 0 ? Yr[r * VCT_TCP] : w.y[r];   // row 0: :1654
       if (j == T - 1) break;
-      if (failed) {
-        for (int r = tid; r < NS; r += nth) y[r] = NAN;
+      if (w.failed) {
+        for (int r = tid; r < NS; r += nth) w.y[r] = NAN;
         continue;
       }
-      const double* uc = Uc + tt;     // inputs of the sample: uc[i * VCT_TC]
-      // per-sample model: linear B u, bilinear A + sum_i u_i B_i, nonlinear [zeta; u]
-      if (!NL) {
-        if (g.kind == 0) {
-          for (int r = tid; r < N; r += nth) {
-            double s = 0.0;
-            for (int i = 0; i < m; ++i) s += Bb[r + (size_t)i * N] * uc[i * VCT_TC];
-            bu[r] = s;
-          }
-        } else {
-          double* Aw = const_cast<double*>(Am);
-          for (int e = tid; e < N * N; e += nth) {
-            double s = Ab[e];
-            for (int i = 0; i < m; ++i) s += uc[i * VCT_TC] * Bb[(size_t)i * N * N + e];
-            Aw[e] = s;
-          }
-        }
-      } else {
-        for (int i = tid; i < m; i += nth) v[NS + i] = uc[i * VCT_TC];
-        for (int r = tid; r < NS; r += nth) v[r] = y[r];
-      }
+      ct_sample_model<NL>(w, Uc + tt, VCT_TC);     // inputs of the sample: Uc[tt + i * VCT_TC]
       __syncthreads();
-      // ---- dopri45 over [0, Ts] from y (kp_ct_rollout_kernel) ----
-      double* k0 = kk;
-      double* k6 = kk + 6 * NS;
-      rhs(y, k0);
-      double loc = 0.0;
-      for (int r = tid; r < NS; r += nth) loc = ct_max(loc, fabs(k0[r] / fmax(fabs(y[r]), thr)));
-      double rh = ct_block_max(loc, red, flip) / (0.8 * pow(rtol, 0.2));
-      double t = 0.0;
-      double h = fmin(hmax, fabs(Ts));
-      if (h * rh > 1.0) h = 1.0 / rh;
-      h = fmax(h, 16.0 * CT_EPS * 1e-300);
-      int attempts = 0;
-      while (t < Ts && !failed) {
-        const double hmin = 16.0 * CT_EPS * fmax(fabs(t), 1e-300);
-        h = fmin(hmax, fmax(hmin, h));
-        if (1.1 * h >= Ts - t) h = Ts - t;
-        bool nofail = true;
-        double err, tnew;
-        for (;;) {
-          for (int s = 1; s < 6; ++s) {
-            double* xin = NL ? v : ((s & 1) ? yt1 : yt0);
-            for (int r = tid; r < NS; r += nth) {
-              double a = 0.0;
-              for (int q = 0; q < s; ++q) a += dp_a(s, q) * kk[q * NS + r];
-              xin[r] = y[r] + h * a;
-            }
-            if (!NL) __syncthreads();
-            rhs(xin, kk + s * NS);
-          }
-          for (int r = tid; r < NS; r += nth) {
-            double a = 0.0;
-            for (int q = 0; q < 6; ++q) a += dp_a(6, q) * kk[q * NS + r];
-            yn[r] = y[r] + h * a;
-            if (NL) v[r] = yn[r];
-          }
-          tnew = t + h;
-          if (!NL) __syncthreads();
-          rhs(yn, k6);
-          double le = 0.0;
-          for (int r = tid; r < NS; r += nth) {
-            double e = 0.0;
-            for (int q = 0; q < 7; ++q) e += dp_e(q) * kk[q * NS + r];
-            le = ct_max(le, fabs(e) / fmax(fmax(fabs(y[r]), fabs(yn[r])), thr));
-            if (!(fabs(yn[r]) < INFINITY)) le = NAN;
-          }
-          err = h * ct_block_max(le, red, flip);
-          ++attempts;
-          if (!(err < INFINITY) || attempts > CT_MAX_ATTEMPTS) { failed = 1; break; }
-          if (err > rtol) {
-            if (h <= hmin) { failed = 1; break; }     // step-size underflow
-            ++nrej;
-            if (nofail) {
-              nofail = false;
-              h = fmax(hmin, h * fmax(0.1, 0.8 * pow(rtol / err, 0.2)));
-            } else {
-              h = fmax(hmin, 0.5 * h);
-            }
-            continue;
-          }
-          break;
-        }
-        if (failed) break;
-        double hnext;
-        if (nofail) {
-          const double temp = 1.25 * pow(err / rtol, 0.2);
-          hnext = temp > 0.2 ? h / temp : 5.0 * h;
-        } else {
-          hnext = h;
-        }
-        t = tnew;
-        ++nacc;
-        { double* tmp = y; y = yn; yn = tmp; }
-        // FSAL: the last stage of the accepted step is the first of the next
-        double* kl = kk + 6 * NS;
-        for (int r = tid; r < NS; r += nth) kk[r] = kl[r];
-        if (NL) for (int r = tid; r < NS; r += nth) v[r] = y[r];
-        h = hnext;
-      }
-      if (failed)
-        for (int r = tid; r < NS; r += nth) y[r] = NAN;
-      __syncthreads();     // y complete before the next sample's model and right-hand side read it
+      ct_integrate<NL>(w, bd);
     }
     __syncthreads();       // the last sample leaves the loop before its barrier
     // ---- the errors of the chunk (kp_validate_kernel) ----
@@ -323,9 +190,9 @@ __global__ __launch_bounds__(256) void kp_validate_ct_kernel(VctArgs g, BasisDev
   if (tid == 0) {
     eo[3 * n] = acc[4 * n] / Td;
     eo[3 * n + 1] = acc[4 * n + 1] / Td;
-    g.status[blockIdx.x] = (failed || acc[4 * n + 2] != 0.0) ? 1 : 0;
-    g.nacc[blockIdx.x] = nacc;
-    g.nrej[blockIdx.x] = nrej;
+    g.status[blockIdx.x] = (w.failed || acc[4 * n + 2] != 0.0) ? 1 : 0;
+    g.nacc[blockIdx.x] = w.nacc;
+    g.nrej[blockIdx.x] = w.nrej;
   }
 }
 
@@ -336,36 +203,14 @@ extern "C" int kp_validate_ct(kp_ctx* ctx, const kp_basis* basis, int model_type
                               const double* Yreal, const double* Wl, const double* yfactor, int want_sim, double Ts, double rtol,
                               double atol, double* err_out, int* status_out, double* Ysim, int* naccept, int* nreject) {
   if (!ctx) return KP_ERR_ARG;
-  if (!basis || !A || !trial_off || !zeta0 || !Yreal || !yfactor || !err_out || !status_out || nmod < 1 || ntr < 1 || N < 1 || m < 0 ||
-      n < 1 || nzeta < 1 || nw < 0)
-    return ctx->fail(KP_ERR_ARG, "kp_validate_ct: bad argument");
-  if (model_type != KP_MODEL_LINEAR && model_type != KP_MODEL_BILINEAR && model_type != KP_MODEL_NONLINEAR)
-    return ctx->fail(KP_ERR_ARG, "kp_validate_ct: unknown model type");
+  const int rc_arg = val_check_args(ctx, "kp_validate_ct", basis, model_type, N, m, n, nzeta, nw, nmod, A, B, ntr, trial_off, zeta0, U,
+                                    Yreal, yfactor, want_sim, err_out, status_out, Ysim);
+  if (rc_arg) return rc_arg;
   if (nw != 0) return ctx->fail(KP_ERR_ARG, "kp_validate_ct: loaded continuous-time models are not supported (nw must be 0)");
-  if (!(std::isfinite(Ts) && Ts > 0 && std::isfinite(rtol) && rtol > 0 && std::isfinite(atol) && atol > 0))
-    return ctx->fail(KP_ERR_ARG, "kp_validate_ct: Ts, rtol and atol must be positive and finite");
+  if (!ct_tol_ok(Ts, rtol, atol)) return ctx->fail(KP_ERR_ARG, "kp_validate_ct: Ts, rtol and atol must be positive and finite");
+  if (N > 512) return ctx->fail(KP_ERR_ARG, "kp_validate_ct: N must be at most 512");
   const bool nl = model_type == KP_MODEL_NONLINEAR, bil = model_type == KP_MODEL_BILINEAR;
   const BasisDev& b = basis->dev;
-  if (b.model_type != model_type)
-    return ctx->fail(KP_ERR_ARG, "kp_validate_ct: the dictionary is of model type " + std::to_string(b.model_type) +
-                                     ", the models of type " + std::to_string(model_type));
-  if (b.N != N || b.m != m || b.nzeta != nzeta)
-    return ctx->fail(KP_ERR_ARG, "kp_validate_ct: N, m and nzeta must be those of the dictionary (" + std::to_string(b.N) + ", " +
-                                     std::to_string(b.m) + ", " + std::to_string(b.nzeta) + ")");
-  if (N > 512) return ctx->fail(KP_ERR_ARG, "kp_validate_ct: N must be at most 512");
-  if (n > N || (nl && n > nzeta))
-    return ctx->fail(KP_ERR_ARG, "kp_validate_ct: n = " + std::to_string(n) + " outputs, but the state has " +
-                                     std::to_string(nl ? nzeta : N) + " entries");
-  if (!nl && !B) return ctx->fail(KP_ERR_ARG, "kp_validate_ct: B required");
-  if (m > 0 && !U) return ctx->fail(KP_ERR_ARG, "kp_validate_ct: U required");
-  if (want_sim && !Ysim) return ctx->fail(KP_ERR_ARG, "kp_validate_ct: Ysim required with want_sim");
-  if (trial_off[0] != 0) return ctx->fail(KP_ERR_ARG, "kp_validate_ct: trial_off must start at 0");
-  for (int q = 0; q < ntr; ++q) {
-    const int64_t Tq = trial_off[q + 1] - trial_off[q];
-    if (Tq < 1) return ctx->fail(KP_ERR_ARG, "kp_validate_ct: trial " + std::to_string(q) + " is empty");
-    if (Tq > INT32_MAX) return ctx->fail(KP_ERR_ARG, "kp_validate_ct: trial " + std::to_string(q) + " is too long");
-  }
-  if ((int64_t)nmod * ntr > INT32_MAX) return ctx->fail(KP_ERR_ARG, "kp_validate_ct: too many (model, trial) pairs");
   const int64_t rows = trial_off[ntr];
   const size_t NS = nl ? nzeta : N;
 

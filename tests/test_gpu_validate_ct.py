@@ -147,13 +147,16 @@ def test_a_stiff_model_rejects_steps_as_the_host_does(ctx):
 
 
 # ---- 2. every dispatch regime and chunk boundary ----------------------------------------------------------------------------
-@pytest.mark.parametrize("mt,nzeta,m,waves,staged,nmod", [
+REGIMES = [
     ("linear", 3, 2, 1, True, 2), ("bilinear", 3, 2, 1, True, 2), ("nonlinear", 3, 2, 1, True, 2),   # N = 10, 10, 21 (nfull 21)
     ("linear", 10, 2, 4, True, 2),                                                                     # N = 66
     ("nonlinear", 8, 3, 4, True, 2),                                                                   # N = nfull = 78
     ("bilinear", 12, 2, 4, False, 2),                      # N = 91: 8 281 doubles > 8 192, A + sum u_i B_i in device scratch
     ("linear", 12, 2, 4, False, 2),                        # N = 91: A read from memory
-    ("nonlinear", 28, 1, 4, False, 1)])                    # N = 465: Kf 28 x 465 = 13 020 doubles read from memory
+    ("nonlinear", 28, 1, 4, False, 1)]                     # N = 465: Kf 28 x 465 = 13 020 doubles read from memory
+
+
+@pytest.mark.parametrize("mt,nzeta,m,waves,staged,nmod", REGIMES)
 def test_every_dispatch_regime_and_chunk_boundary(ctx, mt, nzeta, m, waves, staged, nmod):
     dic, models, rng = ct_case(mt, nzeta, m, 5, nmod)
     N, n = dic.N, nzeta
@@ -174,6 +177,29 @@ def test_every_dispatch_regime_and_chunk_boundary(ctx, mt, nzeta, m, waves, stag
                 assert np.array_equal(sim[i][q], v["y"])
     err2, st2, _, na2, nr2 = ctx.validate_ct(basis, mt, mods, packed, n, fac, TS)
     assert np.array_equal(err2, err, equal_nan=True) and np.array_equal(na2, na) and np.array_equal(nr2, nr) and not st2.any()
+    basis.close()
+
+
+@pytest.mark.parametrize("mt,nzeta,m", [r[:3] for r in REGIMES])
+def test_the_table_and_the_rollout_are_one_integrator(ctx, mt, nzeta, m):
+    """kp_validate_ct_kernel and kp_ct_rollout_kernel run the same code (kp_ct_step.h) on the same start bits - the matrix
+    models' z_0 is the device lift the per-trial val_model route takes - so the samples behind row 0 and the step counts of a
+    pair are those of one kp_rollout_ct / kp_rollout_nl_ct call, bit for bit.  One model, trials of 2 and chunk + 1 rows (a
+    chunk boundary inside the second) in every regime of the dispatch test."""
+    dic, models, rng = ct_case(mt, nzeta, m, 5, 1)
+    n, mo = nzeta, models[0]
+    basis = make_basis(ctx, dic)
+    trials = random_trials(rng, (2, TC + 1), n, m)
+    _, st, sim, na, nr = ctx.validate_ct(basis, mt, *pack([mo], trials, mt), n, np.ones(n), TS, want_sim=True)
+    assert not st.any()
+    for q, v in enumerate(trials):
+        if mt == "nonlinear":
+            Z, a, r, s = ctx.rollout_nl_ct(basis, mo["Kf"], v["y"][0], v["u"], TS)
+        else:
+            z0 = basis.lift(F.LIFT_ECON, v["y"][0])[0]
+            Z, a, r, s = ctx.rollout_ct(mt, mo["A"], mo["B"], z0, v["u"], n, TS)
+        assert s == 0 and a > 0 and Z.shape == sim[0][q].shape
+        assert np.array_equal(sim[0][q][1:], Z[1:]) and (na[0, q], nr[0, q]) == (a, r), (q, na[0, q], nr[0, q], a, r)
     basis.close()
 
 
