@@ -53,7 +53,13 @@ int kp_device_info(const kp_ctx* ctx, char* name, int name_len, int* num_cu, int
  * most recent lasso batch, 9: its number of columns (kp_symm_gemm2_kernel: the FISTA iteration's product); 10: flop per snapshot pair the most recent
  * fused lift+Gram launch EXECUTES on the matrix pipe (padding and, for dim_red dictionaries, the projection included); 11: host
  * milliseconds the most recent lasso batch spent in the regularisation-path homotopy (0: the projected-gradient iteration
- * finished every value; kp_fit_lasso below). */
+ * finished every value; kp_fit_lasso below); 12: how many pipelined fits (kp_fit with K_out == NULL) of one dictionary and snapshot
+ * count may share one Gram launch and one partial reduction (environment variable KP_GRAM_GROUP, read once; 1: none do) - timers 0
+ * and 6 are then per fit: the durations of the launches in the mean, divided by the number of fits those launches served.  13: the
+ * number of fits served by the launches that timer 7 counts (timer 7 itself stays the number of launches).  A fit of a group of n sums its snapshots
+ * over 1 / n of the splits of a lone launch - the same terms in another fixed order - so the last bits of a pipelined K depend on
+ * how many fits were queued with it (5e-14 at W = 336 between a member of a group of 8 and of 4); only fits of fewer than 512
+ * snapshot tiles per split (about 3e5 pairs at W = 336) are grouped. */
 int kp_timer_get(const kp_ctx* ctx, int which, double* ms);
 /* Device pointer + byte size of the library stream's raw handle, for profilers/benchmarks
  * that want to bracket work with their own HIP events: returns hipStream_t as void*. */

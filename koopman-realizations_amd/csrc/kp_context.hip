@@ -41,6 +41,7 @@ extern "C" int kp_create(int device_id, kp_ctx** out) {
   kp_ctx* c = new kp_ctx();
   c->device = device_id;
   c->test_hooks = getenv("KP_TEST_HOOKS") != nullptr;
+  c->timers[12] = (double)kp_gram_group_size();
   // Events order work between this context's two streams and time kernels; neither needs the system-scope release
   // (L2 write-back towards the host) that a default event performs after every kernel it follows - results reach the
   // host through explicit copies.  KP_EVENT_SYSTEM_FENCE=1 restores the default.
@@ -53,6 +54,7 @@ extern "C" int kp_create(int device_id, kp_ctx** out) {
   }
   for (int i = 0; i < 6; ++i) (void)hipEventCreateWithFlags(&c->evp[i], evf);
   for (int i = 0; i < 2 * 64; ++i) (void)hipEventCreateWithFlags(&c->ring[i], evf);
+  for (int i = 0; i < 64; ++i) (void)hipEventCreateWithFlags(&c->ring_red[i], evf);
   (void)hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking);
   (void)hipEventCreateWithFlags(&c->ev_gram_done, hipEventDisableTiming | evf);
   (void)hipEventCreateWithFlags(&c->ev_pad_done, hipEventDisableTiming | evf);
@@ -74,6 +76,8 @@ extern "C" int kp_create(int device_id, kp_ctx** out) {
 
 extern "C" int kp_destroy(kp_ctx* c) {
   if (!c) return KP_OK;
+  (void)hipSetDevice(c->device);
+  (void)kp_flush_grams(c);            // (queued Gram launches: nothing may point into what is freed below)
   (void)kp_comm_destroy(c);
   (void)hipSetDevice(c->device);
   kp_stage_destroy(c);
@@ -97,6 +101,8 @@ extern "C" int kp_destroy(kp_ctx* c) {
     if (c->evp[i]) (void)hipEventDestroy(c->evp[i]);
   for (int i = 0; i < 2 * 64; ++i)
     if (c->ring[i]) (void)hipEventDestroy(c->ring[i]);
+  for (int i = 0; i < 64; ++i)
+    if (c->ring_red[i]) (void)hipEventDestroy(c->ring_red[i]);
   (void)hipEventDestroy(c->ev0);
   (void)hipEventDestroy(c->ev1);
   (void)hipStreamDestroy(c->stream);
@@ -154,7 +160,7 @@ void* kp_pinned_scratch(kp_ctx* ctx, size_t bytes) {
 }
 
 extern "C" int kp_timer_get(const kp_ctx* c, int which, double* ms) {
-  if (!c || !ms || which < 0 || which >= 12) return KP_ERR_ARG;
+  if (!c || !ms || which < 0 || which >= 14) return KP_ERR_ARG;
   *ms = c->timers[which];
   return KP_OK;
 }
@@ -400,6 +406,7 @@ extern "C" int kp_basis_create(kp_ctx* ctx, const kp_basis_desc* d, kp_basis** o
 extern "C" int kp_basis_destroy(kp_basis* b) {
   if (!b) return KP_OK;
   (void)hipSetDevice(b->ctx->device);
+  (void)kp_flush_grams(b->ctx);       // (a queued Gram launch reads the dictionary's recipes and plan)
   if (b->d_cols) (void)hipFree(b->d_cols);
   if (b->d_exps) (void)hipFree(b->d_exps);
   if (b->d_centres) (void)hipFree(b->d_centres);

@@ -866,24 +866,36 @@ static int read_chol_info(kp_ctx* ctx, int W, int ncols, int* bad, const double*
 // timers: 0 = fused lift+Gram kernel, 6 = partial-tile reduction, 1 = solve (when run)
 static void collect_gram_timers(kp_ctx* ctx, bool solved) {
   float ms = 0;
+  bool red_done = false;
   if (ctx->ring_n > 0) {                          // pipelined fits: mean over the last ring_n Gram launches
-    double sum = 0.0;
-    int cnt = 0;
+    // (a launch of the Gram queue serves ring_members fits: time per FIT = sum of the launches / sum of their fits; the same for
+    // the reductions that were timed)
+    double sum = 0.0, rsum = 0.0;
+    int cnt = 0, fits = 0, rfits = 0;
     for (int i = 0; i < ctx->ring_n; ++i) {
       const int p = (ctx->ring_pos - 1 - i + 2 * 64) % 64;
       if (hipEventElapsedTime(&ms, ctx->ring[2 * p], ctx->ring[2 * p + 1]) == hipSuccess) {
         sum += ms;
+        fits += std::max(1, ctx->ring_members[p]);
         ++cnt;
+        if (ctx->ring_has_red[p] && hipEventElapsedTime(&ms, ctx->ring[2 * p + 1], ctx->ring_red[p]) == hipSuccess) {
+          rsum += ms;
+          rfits += std::max(1, ctx->ring_members[p]);
+        }
       }
     }
-    if (cnt) ctx->timers[0] = (float)(sum / cnt);
+    if (cnt) ctx->timers[0] = (float)(sum / fits);
     ctx->timers[7] = (float)cnt;
+    ctx->timers[13] = (float)fits;
     ctx->ring_n = 0;
+    if (rfits) ctx->timers[6] = (float)(rsum / rfits);
+    red_done = rfits > 0;
   } else if (hipEventElapsedTime(&ms, ctx->evp[0], ctx->evp[1]) == hipSuccess) {
     ctx->timers[0] = ms;
     ctx->timers[7] = 1.0f;
+    ctx->timers[13] = 1.0f;
   }
-  if (hipEventElapsedTime(&ms, ctx->evp[ctx->reduce_timed_from], ctx->evp[2]) == hipSuccess) ctx->timers[6] = ms;
+  if (!red_done && hipEventElapsedTime(&ms, ctx->evp[ctx->reduce_timed_from], ctx->evp[2]) == hipSuccess) ctx->timers[6] = ms;
   if (solved && hipEventElapsedTime(&ms, ctx->evp[2], ctx->evp[3]) == hipSuccess) ctx->timers[1] = ms;
   (void)hipGetLastError();   // an event pair that was not recorded in this mode leaves a sticky error behind: not a failure
 }
@@ -995,7 +1007,54 @@ static int solve_batch_size() {
   return v;
 }
 
+// Fits per Gram launch of the deferred-solve pipeline: KP_GRAM_GROUP (read once; 1: every fit is launched at once, on its own)
+int kp_gram_group_size() {
+  static const int v = [] { const char* e = getenv("KP_GRAM_GROUP"); return e ? std::min(KP_GRAM_GROUP_MAX, std::max(1, atoi(e))) : 8; }();   // (2 / 4 / 8 measured: DESIGN 6)
+  return v;
+}
+
+// The queued fits as ONE Gram launch and ONE partial reduction.  Called by everything that enqueues behind them, reads a result
+// or frees what they point to (DESIGN 3.2 lists the entries).
+int kp_flush_grams(kp_ctx* ctx) {
+  const int n = ctx->pend_ngrams;
+  if (n == 0) return KP_OK;
+  ctx->pend_ngrams = 0;                 // (whatever happens below: the queue is not launched twice)
+  // A launch that fails leaves the members' [G | C] slots unwritten: they - the n newest of the solve batch and of the result
+  // ring - are taken back, so that no later solve factors them and no kp_fit_get_K serves them
+  auto failed = [&](int rc) {
+    ctx->pend_solves = std::max(0, ctx->pend_solves - n);
+    ctx->async_count = std::max(0, ctx->async_count - n);
+    return rc;
+  };
+  if (hipError_t e = hipSetDevice(ctx->device); e != hipSuccess)
+    return failed(ctx->fail(KP_ERR_HIP, std::string("kp_flush_grams: hipSetDevice: ") + hipGetErrorString(e)));
+  // (an acquire only makes the stream wait for a member's refill: members acquired before a failing one hold nothing that would
+  // have to be released - kp_snaps_release marks a READ, and nothing has read; the failing member's refill stays pending)
+  for (int f = 0; f < n; ++f) {
+    const bool was_pending = ctx->pend_grams[f]->dma_pending;
+    if (hipError_t e = kp_snaps_acquire(ctx->pend_grams[f], ctx->stream); e != hipSuccess) {
+      ctx->pend_grams[f]->dma_pending = was_pending;
+      return failed(ctx->fail(KP_ERR_HIP, std::string("kp_flush_grams: ") + hipGetErrorString(e)));
+    }
+  }
+  ctx->reserve_cus = 0;
+  ctx->reduce_stream = nullptr;
+  ctx->reduce_timed_from = 1;
+  ctx->ring_timing = true;
+  ctx->ring_group = true;
+  const int rc = kp_gram3_launch_group(ctx, ctx->pend_gram_basis, ctx->pend_grams, n, ctx->pend_gram_gc);
+  ctx->ring_timing = false;
+  ctx->ring_group = false;
+  if (rc) return failed(rc);
+  for (int f = 0; f < n; ++f) KP_HIP(ctx, kp_snaps_release(ctx->pend_grams[f], ctx->stream));
+  return KP_OK;
+}
+
 static int flush_solves(kp_ctx* ctx) {
+  {
+    int rcg = kp_flush_grams(ctx);
+    if (rcg) return rcg;
+  }
   if (ctx->pend_solves == 0) return KP_OK;
   const int W = ctx->pend_W;
   KP_HIP(ctx, hipEventRecord(ctx->ev_solve0, ctx->stream));
@@ -1065,6 +1124,26 @@ extern "C" int kp_fit(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* sn
       }
       if (ctx->pend_solves == 0) ctx->pend_first = ctx->async_count;
       double* GCs = ctx->GC + (size_t)ctx->pend_solves * 2 * W * W;
+      // Fits of the Kronecker kernel's plain form wait for up to KP_GRAM_GROUP of their kind (same dictionary, snapshot count and
+      // width: any change has drained the pipeline above) and share ONE Gram launch and ONE partial reduction: each gets a
+      // share of the chip's wave slots, so its split partials - written and read back once per fit - are 1 / group of a
+      // lone launch's.  The solves are deferred anyway: no K is available before the caller synchronises.
+      if (kp_gram_group_size() > 1 && kp_gram3_groupable(ctx, basis, snaps)) {
+        if (snaps->Ns > 0 && (!snaps->alpha || !snaps->beta || (snaps->m > 0 && !snaps->u)))
+          return ctx->fail(KP_ERR_ARG, "kp_fit: the snapshot object holds no device arrays (a failed kp_snapshots_update?)");
+        if (ctx->pend_ngrams == 0) ctx->pend_gram_gc = GCs;
+        ctx->pend_gram_basis = basis;
+        ctx->pend_grams[ctx->pend_ngrams++] = snaps;
+        ++ctx->pend_solves;
+        ++ctx->async_count;
+        ctx->async_pending = true;
+        // (a full group, or no room left in the solve batch - the batch can be as small as the result ring)
+        if (ctx->pend_solves >= sbatch) return flush_solves(ctx);
+        if (ctx->pend_ngrams >= kp_gram_group_size()) return kp_flush_grams(ctx);
+        return KP_OK;
+      }
+      rc = kp_flush_grams(ctx);
+      if (rc) return rc;
       ctx->reserve_cus = 0;
       ctx->reduce_stream = nullptr;
       ctx->ring_timing = true;

@@ -111,6 +111,15 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
   const int logical = (int)blockIdx.x < per_xcd * 8 ? ((int)blockIdx.x % 8) * per_xcd + (int)blockIdx.x / 8 : (int)blockIdx.x;
   const int super = logical % a.nsuper;
   const int split = logical / a.nsuper;
+  // Pipelined fits that share the launch (INL form without a projection; kp_fit.hip's Gram queue): fit `fit` owns the global
+  // splits [fit nsplit_fit, (fit + 1) nsplit_fit) - it walks ITS snapshots in nsplit_fit pieces and reads its own arrays, and its
+  // partials land at the global split index, where the reduction finds them.  Both are wave-uniform (scalar).
+  constexpr bool GRP = !PCS && !EXT && !PRE;
+  const int fit = GRP ? __builtin_amdgcn_readfirstlane(split / a.nsplit_fit) : 0;
+  const int split_local = split - fit * a.nsplit_fit;
+  const double* const src_alpha = GRP ? a.grp[fit].alpha : a.alpha;
+  const double* const src_beta = GRP ? a.grp[fit].beta : a.beta;
+  const double* const src_u = GRP ? a.grp[fit].u : a.u;
   const int job = super * 4 + wave;
   const int nzm = b.nzeta + b.m;
   const int nrawrows = 2 * nzm;
@@ -207,7 +216,7 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
     }
   }
 
-  const int64_t kt0 = (int64_t)split * a.ktiles_per_split;
+  const int64_t kt0 = (int64_t)split_local * a.ktiles_per_split;
   const int64_t ktiles_total = (a.Ns + KT3 - 1) / KT3;
   const int nkt = (int)max((int64_t)0, min((int64_t)a.ktiles_per_split, ktiles_total - kt0));
 
@@ -230,7 +239,7 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
     ld_on[j] = e < nrawrows * KT3;
     const int r = ld_on[j] ? e / KT3 : 0;
     const int rr = r % nzm;
-    const double* src = rr < b.nzeta ? ((r < nzm ? a.alpha : a.beta) + (int64_t)rr * a.Ns) : (a.u + (int64_t)(rr - b.nzeta) * a.Ns);
+    const double* src = rr < b.nzeta ? ((r < nzm ? src_alpha : src_beta) + (int64_t)rr * a.Ns) : (src_u + (int64_t)(rr - b.nzeta) * a.Ns);
     ld_ptr[j] = src + kt0 * KT3 + ld_s;
     ld_isz[j] = ld_on[j] && rr < b.nzeta;
   }
@@ -245,7 +254,7 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
       const int gi = tid + q * 256;
       g_on[q] = gi < 2 * a.ng * KT3;
       const int gc = g_on[q] ? (gi / KT3) % a.ng : 0, gside = g_on[q] ? gi / (KT3 * a.ng) : 0;
-      g_ptr[q] = (gside ? a.beta : a.alpha) + kt0 * KT3 + ld_s;
+      g_ptr[q] = (gside ? src_beta : src_alpha) + kt0 * KT3 + ld_s;
       g_dst[q] = CA + (1 + gside * a.ng + gc) * PST3 + ld_s;
       g_cen[q] = GC03 + gc * b.nzeta;
     }
@@ -321,7 +330,7 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
   int tb_inc = KT3;
   {
     const int rr = tb_r % nzm;
-    tb_ptr = (rr < b.nzeta ? ((tb_r < nzm ? a.alpha : a.beta) + (int64_t)rr * a.Ns) : (a.u + (int64_t)(rr - b.nzeta) * a.Ns)) + kt0 * KT3 + ld_s;
+    tb_ptr = (rr < b.nzeta ? ((tb_r < nzm ? src_alpha : src_beta) + (int64_t)rr * a.Ns) : (src_u + (int64_t)(rr - b.nzeta) * a.Ns)) + kt0 * KT3 + ld_s;
     if (tb_r == nrawrows) { tb_ptr = kp_gram3_ones; tb_inc = 0; }
   }
   const uint32_t tb_dst = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) double*)(sm + tb_r * RB + ld_s);
@@ -678,6 +687,8 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
 // blockDim.x / 64 = 4, 8 or 16 waves share the split sum (the launcher picks by the split count: a dim_red fit at the arm data's
 // size has 167 splits of 184 KB - four waves walked 42 dependent-latency loads each, 14 us for a 23 us Gram kernel), each wave
 // with four loads in flight; every order is fixed: bitwise reproducible.
+// blockIdx.y = fit of a group launch (kp_gram3_kernel, GRP): it sums that fit's nsplit splits - the global splits
+// [y nsplit, (y + 1) nsplit) - into that fit's [G | C] slot, 2 W^2 doubles behind the previous one.
 __global__ __launch_bounds__(1024) void kp_gram3_reduce_kernel(const double* __restrict__ part, int nsplit, int njobs, int NQ, int NWT,
                                                               int BM, const uint32_t* __restrict__ desc, int G4, int N, int W,
                                                               double* __restrict__ G, double* __restrict__ C, int tup) {
@@ -687,7 +698,9 @@ __global__ __launch_bounds__(1024) void kp_gram3_reduce_kernel(const double* __r
   const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, nwv = blockDim.x >> 6;
   __shared__ double red[16][64];
   const size_t per_split = (size_t)njobs * NQ * NWT * 64;
-  const double* src = part + (size_t)idx * 64 + l;
+  const double* src = part + (size_t)blockIdx.y * nsplit * per_split + (size_t)idx * 64 + l;
+  G += (size_t)blockIdx.y * 2 * W * W;
+  C += (size_t)blockIdx.y * 2 * W * W;
   double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
   int p = wv;
   for (; p + 3 * nwv < nsplit; p += 4 * nwv) {
@@ -915,21 +928,68 @@ bool kp_gram3_applicable(const kp_basis* basis) {
          b.m >= 1 && b.m <= 3 && (2 * (b.nzeta + b.m) + 1) * KT3 <= 256 && 2 * (b.nzeta + b.m) * 4 + 4 <= NIDMAX3;   // (+ 1: the constant's table row has a thread)
 }
 
-int kp_gram3_launch(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapshots* s, double* GC_dev) {
+// eight-wave workgroups (kp_gram6.hip), a round 4 experiment: KP_GRAM6=1, read once
+static bool gram6_on() {
+  static const bool on = getenv("KP_GRAM6") != nullptr;
+  return on;
+}
+
+// the dictionary's plan, built on first use
+static int gram3_plan(kp_ctx* ctx, kp_basis* basis) {
+  if (basis->plan3) return KP_OK;
+  const BasisDev& b = basis->dev;
+  const int N = b.N, BM = b.m, NWT = (BM + 1) * (BM + 2) / 2;
+  // fourier / gaussian tables: the transcendental code's constants and temporaries cost ~40 registers, so fewer quads
+  // (accumulators) per wave or the kernel spills (measured: 4 quads per wave is the fastest cap, tools/gram_shapes_probe.py)
+  static const int ext_cap = [] { const char* e = getenv("KP_GRAM3_EXT_NQ"); return e ? atoi(e) : 4; }();
+  // round 4 experiment (KP_GRAM6=1): eight-wave workgroups, the weighted A operands in LDS (kp_gram6.hip)
+  const bool g6 = gram6_on() && BM == 3 && b.k_pcs == 0 && !gram3_ext(basis) && kp_gram6_serves(7, (N + 3) / 4);
+  return g6 ? make_plan3(ctx, N, NWT, 7, &basis->plan3, 8, 7)
+            : make_plan3(ctx, N, NWT, b.k_pcs > 0 ? 4 : gram3_ext(basis) ? ext_cap : 6, &basis->plan3);     // (one plan serves both forms of a dim_red / fourier / gaussian fit)
+}
+
+// workgroup slots of the chip for this plan's kernel
+static int64_t gram3_slots(const kp_ctx* ctx, const kp_gram3_plan& plan, int* ncu_out = nullptr, int* wgpcu_out = nullptr) {
+  int ncu = ctx->num_cu > 0 ? ctx->num_cu : 256;
+  int wg_per_cu = plan.wpw == 8 ? 1 : 2;              // __launch_bounds__(256, 2): two workgroups share a CU (kp_gram6: one of eight waves)
+  if (const char* ov = getenv("KP_GRAM3_WGPCU")) wg_per_cu = std::max(1, atoi(ov));
+  if (ncu_out) *ncu_out = ncu;
+  if (wgpcu_out) *wgpcu_out = wg_per_cu;
+  return (int64_t)std::max(8, ncu - ctx->reserve_cus) * wg_per_cu;
+}
+
+// Fits that may share a Gram launch (kp_fit.hip's queue of pipelined fits): the in-kernel-lift monomial form of kp_gram3_kernel -
+// no projection, no fourier / gaussian table entries, hence no prelift buffer either - with four-wave workgroups; and only while
+// a lone launch's splits are shorter than KP_GRAM_GROUP_MAX_KPS tiles.  What sharing saves is a fixed cost per fit (head, write-out
+// and reduction of one accumulator set per wave slot: ~30 us at W = 336, some 15 tile times); what it costs is whole-split
+// granularity, 1 - 1.4 % of the kernel time (a fit of a group of 8 gets 9 of the 73 splits: 504 of 512 slots) - measured at
+// 1e6 / 1e7 pairs (1 713 / 17 124 tiles per split) the group was 1.3 / 1.5 % SLOWER per fit, at 1e5 (172) 4.6 % faster.  Where
+// between 172 and 1 713 the two cross was NOT measured: 512 is the estimate from those figures (fixed saving ~22 us = 1.36 % of a
+// kernel of 1.6 ms, ~800 tiles per split at W = 336), rounded down.
+bool kp_gram3_groupable(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapshots* s) {
   kp_basis* basis = const_cast<kp_basis*>(basis_c);
   const BasisDev& b = basis->dev;
-  if (s->nzeta != b.nzeta || s->m != b.m) return ctx->fail(KP_ERR_ARG, "kp_fit_gram: snapshot/basis dimension mismatch");
+  if (!(kp_gram3_applicable(basis) && b.k_pcs == 0 && !gram3_ext(basis) && !gram6_on() && s->nzeta == b.nzeta && s->m == b.m)) return false;
+  if (gram3_plan(ctx, basis) != KP_OK || basis->plan3->wpw == 8) return false;      // (a plan that cannot be built: the immediate dispatch reports it)
+  static const int64_t max_kps = [] { const char* e = getenv("KP_GRAM_GROUP_MAX_KPS"); return e ? (int64_t)atoll(e) : (int64_t)512; }();
+  const int64_t ktiles = (s->Ns + KT3 - 1) / KT3, nsplit = std::max<int64_t>(1, gram3_slots(ctx, *basis->plan3) / basis->plan3->nsuper);
+  return (ktiles + nsplit - 1) / nsplit < max_kps;
+}
+
+// ss[0 .. n): the snapshot objects of n fits of one dictionary and ONE snapshot count (n > 1: kp_gram3_groupable); their [G | C]
+// pairs go to GC_dev + f 2 W^2.  The launch is dealt over the fits: nsplit_fit = max(1, (slots / nsuper) / n) splits each.  n = 1
+// is the launch of a single fit, bit for bit.
+static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapshots* const* ss, int n, double* GC_dev) {
+  kp_basis* basis = const_cast<kp_basis*>(basis_c);
+  const BasisDev& b = basis->dev;
+  const kp_snapshots* s = ss[0];
+  if (n < 1 || n > KP_GRAM_GROUP_MAX) return ctx->fail(KP_ERR_ARG, "kp_fit_gram: bad group size");
+  for (int f = 0; f < n; ++f)
+    if (ss[f]->nzeta != b.nzeta || ss[f]->m != b.m || ss[f]->Ns != s->Ns) return ctx->fail(KP_ERR_ARG, "kp_fit_gram: snapshot/basis dimension mismatch");
   const int W = b.W, N = b.N;
   const int BM = b.m, NWT = (BM + 1) * (BM + 2) / 2;
-  if (!basis->plan3) {
-    // fourier / gaussian tables: the transcendental code's constants and temporaries cost ~40 registers, so fewer quads
-    // (accumulators) per wave or the kernel spills (measured: 4 quads per wave is the fastest cap, tools/gram_shapes_probe.py)
-    static const int ext_cap = [] { const char* e = getenv("KP_GRAM3_EXT_NQ"); return e ? atoi(e) : 4; }();
-    // round 4 experiment (KP_GRAM6=1): eight-wave workgroups, the weighted A operands in LDS (kp_gram6.hip)
-    static const bool g6_on = getenv("KP_GRAM6") != nullptr;
-    const bool g6 = g6_on && BM == 3 && b.k_pcs == 0 && !gram3_ext(basis) && kp_gram6_serves(7, (N + 3) / 4);
-    int rc = g6 ? make_plan3(ctx, N, NWT, 7, &basis->plan3, 8, 7)
-                : make_plan3(ctx, N, NWT, b.k_pcs > 0 ? 4 : gram3_ext(basis) ? ext_cap : 6, &basis->plan3);     // (one plan serves both forms of a dim_red / fourier / gaussian fit)
+  {
+    int rc = gram3_plan(ctx, basis);
     if (rc) return rc;
   }
   kp_gram3_plan& plan = *basis->plan3;
@@ -937,20 +997,19 @@ int kp_gram3_launch(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapshots* s,
   const bool ext = gram3_ext(basis);
   
   int64_t ktiles = (s->Ns + KT3 - 1) / KT3;
-  int ncu = ctx->num_cu > 0 ? ctx->num_cu : 256;
-  int wg_per_cu = plan.wpw == 8 ? 1 : 2;              // __launch_bounds__(256, 2): two workgroups share a CU (kp_gram6: one of eight waves)
-  if (const char* ov = getenv("KP_GRAM3_WGPCU")) wg_per_cu = std::max(1, atoi(ov));
-  int64_t slots = (int64_t)std::max(8, ncu - ctx->reserve_cus) * wg_per_cu;
-  int nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(ktiles, slots / plan.nsuper > 0 ? slots / plan.nsuper : 1));
+  int ncu, wg_per_cu;
+  const int64_t slots = gram3_slots(ctx, plan, &ncu, &wg_per_cu);
+  // (per fit: the fits of a group launch share the chip)
+  int nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(ktiles, slots / plan.nsuper / n > 0 ? slots / plan.nsuper / n : 1));
   int kps = (int)((ktiles + nsplit - 1) / nsplit);
   if (kps < 1) kps = 1;
   nsplit = (int)std::max<int64_t>(1, (ktiles + kps - 1) / kps);
   size_t per_split = (size_t)plan.njobs * plan.nq * NWT * 64;
   // asynchronous fits: two partial buffers, so that the next Gram kernel may run while the solve stream reduces this one
-  const size_t part_bytes = ((size_t)nsplit * per_split * 8 + 255) & ~(size_t)255;
+  const size_t part_bytes = ((size_t)n * nsplit * per_split * 8 + 255) & ~(size_t)255;
   // sized for the largest split count of this dictionary at once: a workspace that grows with the snapshot count would put
   // a hipFree + hipMalloc of ~80 MB (17 ms, and a device synchronisation) into the first large fit of a running pipeline
-  const size_t part_max = ((size_t)std::max<int64_t>(nsplit, (int64_t)ncu * wg_per_cu / plan.nsuper) * per_split * 8 + 255) & ~(size_t)255;
+  const size_t part_max = ((size_t)std::max<int64_t>((int64_t)n * nsplit, (int64_t)ncu * wg_per_cu / plan.nsuper) * per_split * 8 + 255) & ~(size_t)255;
   char* part_base = (char*)ctx->workspace(4, part_max * (ctx->reduce_stream ? 2 : 1));
   if (!part_base) return ctx->fail(KP_ERR_HIP, "kp_fit_gram: out of device memory");
   double* part = (double*)(part_base + (ctx->reduce_stream ? (size_t)ctx->part_flip * part_bytes : 0));
@@ -961,6 +1020,7 @@ int kp_gram3_launch(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapshots* s,
   // (tools/arm_shape_latency.py with KP_GRAM3_PRELIFT_MIN_NS=0).  Below a few thousand pairs the second launch is not worth it.
   static const int64_t pre_min_ns = [] { const char* e = getenv("KP_GRAM3_PRELIFT_MIN_NS"); return e ? (int64_t)atoll(e) : (int64_t)6000; }();
   bool pre = gram3_prelift(basis) && s->Ns >= pre_min_ns;
+  if (n > 1 && (pre || b.k_pcs > 0 || ext || plan.wpw == 8)) return ctx->fail(KP_ERR_ARG, "kp_fit_gram: these fits cannot share a launch");
   const int pre_rl = 8 * plan.G4 + 12;
   double* pre_buf = nullptr;
   if (pre) {
@@ -1005,7 +1065,9 @@ int kp_gram3_launch(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapshots* s,
   a.nfull4 = nfull4;
   a.pre = pre_buf;
   a.pre_rl = pre_rl;
-  const int grid = plan.nsuper * nsplit;
+  a.nsplit_fit = nsplit;
+  for (int f = 0; f < n; ++f) a.grp[f] = Gram3Src{ss[f]->alpha, ss[f]->beta, ss[f]->u};
+  const int grid = plan.nsuper * nsplit * n;
   // every event record is a barrier packet the command processor works through between two Gram kernels: the
   // pipelined path keeps two (kernel start / end; the end also releases the reduction on the solve stream)
   const bool pipelined = ctx->reduce_stream || ctx->ring_timing;
@@ -1013,10 +1075,20 @@ int kp_gram3_launch(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapshots* s,
   hipEvent_t ev_start = ctx->evp[0], ev_end = ctx->evp[1];
   // deferred-solve pipeline: every event record is a barrier packet between two Gram kernels, so only every 4th launch
   // is timed (the mean over the ring is what kp_synchronize reports)
-  const bool timed = !ctx->ring_timing || (ctx->ring_skip++ & 3) == 0;
+  // A group launch (ring_group: the Gram queue of kp_fit.hip, group size > 1) of several fits is always timed - one event pair
+  // per group is the packet rate of every 4th single launch - and so is its reduction (ring_red, timer 6).  A group of ONE
+  // keeps the every-4th rule and records no third event.
+  const bool timed = !ctx->ring_timing || (ctx->ring_group && n > 1) || (ctx->ring_skip++ & 3) == 0;
+  hipEvent_t ev_red = nullptr;
   if (pipelined && timed) {                       // pipelined fits: a ring of event pairs, averaged at kp_synchronize
     ev_start = ctx->ring[2 * ctx->ring_pos];
     ev_end = ctx->ring[2 * ctx->ring_pos + 1];
+    ctx->ring_members[ctx->ring_pos] = n;
+    ctx->ring_has_red[ctx->ring_pos] = false;
+    if (ctx->ring_timing && ctx->ring_group && n > 1) {   // (a group of one records what a single launch recorded before: nothing behind its reduction)
+      ev_red = ctx->ring_red[ctx->ring_pos];
+      ctx->ring_has_red[ctx->ring_pos] = ev_red != nullptr;
+    }
     ctx->ring_pos = (ctx->ring_pos + 1) % 64;
     if (ctx->ring_n < 64) ++ctx->ring_n;
   }
@@ -1047,9 +1119,10 @@ int kp_gram3_launch(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapshots* s,
     ctx->solve_chained = true;                      // the solve stream already waits for this Gram kernel
   }
   ctx->reduce_timed_from = ctx->reduce_stream ? 4 : 1;
-  hipLaunchKernelGGL(kp_gram3_reduce_kernel, dim3(plan.njobs * plan.nq * NWT), dim3(nsplit >= 128 ? 1024 : nsplit >= 32 ? 512 : 256), 0, rs, part, nsplit, plan.njobs,
+  hipLaunchKernelGGL(kp_gram3_reduce_kernel, dim3(plan.njobs * plan.nq * NWT, n), dim3(nsplit >= 128 ? 1024 : nsplit >= 32 ? 512 : 256), 0, rs, part, nsplit, plan.njobs,
                      plan.nq, NWT, BM, plan.desc, plan.G4, N, W, GC_dev, GC_dev + (size_t)W * W, plan.wpw != 8 && gram3_tup(BM) ? 1 : 0);
   KP_HIP(ctx, hipGetLastError());
+  if (ev_red) KP_HIP(ctx, hipEventRecord(ev_red, rs));
   if (!pipelined) KP_HIP(ctx, hipEventRecord(ctx->ev1, rs));
   if (!ctx->ring_timing) KP_HIP(ctx, hipEventRecord(ctx->evp[2], rs));
   ctx->gram_flops_per_pair = (double)W * (W + 1) + 2.0 * W * W;
@@ -1057,6 +1130,12 @@ int kp_gram3_launch(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapshots* s,
   // each; dim_red: + the projection pcs' psi of every workgroup of a split (2 x nfull4 / 4 MFMAs per wave and tile)
   ctx->timers[10] = (double)plan.njobs * plan.nq * NWT * 128.0 + (b.k_pcs > 0 && !pre ? (double)plan.nsuper * nfull4 * 128.0 : 0.0);
   return KP_OK;
+}
+
+int kp_gram3_launch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s, double* GC_dev) { return gram3_launch_n(ctx, basis, &s, 1, GC_dev); }
+
+int kp_gram3_launch_group(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* const* ss, int n, double* GC_dev) {
+  return gram3_launch_n(ctx, basis, ss, n, GC_dev);
 }
 
 

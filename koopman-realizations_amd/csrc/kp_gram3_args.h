@@ -3,6 +3,8 @@
 #pragma once
 #include "kp_internal.h"
 
+struct Gram3Src { const double *alpha, *beta, *u; };
+
 struct Gram3Args {
   BasisDev b;
   const double* alpha;   // allocated with >= 64 doubles of zero padding (kp_snapshots_upload): prefetch never leaves the buffer
@@ -27,6 +29,11 @@ struct Gram3Args {
   // zeros] of the econ lift as [entry][snapshot], zeros past Ns; pre_rl = entries per snapshot
   const double* pre = nullptr;
   int pre_rl = 0;
+  // A launch may serve several pipelined fits of one dictionary and snapshot count (kp_gram3_kernel's in-kernel-lift monomial
+  // form only): fit f owns the global splits [f nsplit_fit, (f + 1) nsplit_fit) and reads the arrays grp[f]; a launch of one fit
+  // has nsplit_fit = its split count and grp[0] = (alpha, beta, u)
+  int nsplit_fit = 1 << 30;
+  Gram3Src grp[KP_GRAM_GROUP_MAX] = {};
 };
 
 // one job per wave: kp_gram6_kernel<NQ, G4C> (kp_gram6.hip); hipErrorInvalidValue when no instantiation serves (nq, G4)

@@ -11,6 +11,7 @@
 #include "koopman_hip.h"
 
 #define KP_MAX_VARS 32
+#define KP_GRAM_GROUP_MAX 8   // pipelined fits that may share one Gram launch (kp_fit.hip: KP_GRAM_GROUP)
 
 void kp_set_global_error(const std::string& s);
 // kp_batch.hip: the device blocks of a new kp_traj (0 Y, 1 U, 2 Yv, 3 Uv), marked as put - the caller fills them on the
@@ -51,6 +52,15 @@ struct kp_ctx {
   int pend_solves = 0, pend_first = 0;
   bool ring_timing = false;           // Gram launchers time themselves with the event ring and record nothing else
   unsigned ring_skip = 0;
+  // Gram queue of the deferred-solve pipeline (kp_fit.hip): up to KP_GRAM_GROUP fits of one dictionary and snapshot count wait
+  // here and run as ONE Gram launch and ONE partial reduction (kp_gram3_launch_group); their [G | C] slots in the ring are
+  // consecutive, pend_gram_gc the first.  Everything that enqueues on `stream`, reads a result or frees what a queued fit
+  // points to launches the queue first (kp_flush_grams).
+  const kp_snapshots* pend_grams[KP_GRAM_GROUP_MAX] = {};
+  int pend_ngrams = 0;
+  const kp_basis* pend_gram_basis = nullptr;
+  double* pend_gram_gc = nullptr;
+  bool ring_group = false;            // set around a launch of the Gram queue: the launch and its reduction are timed per group
   kp_comm_state* comm = nullptr;      // set by kp_comm_create: rank / world / RCCL communicator
   std::atomic<bool> comm_abandoned{false};   // kp_comm_abandon: a bootstrap still blocked in another thread must not publish `comm`
   bool gc_preloaded = false;          // kp_multi_fit_sharded: ctx->GC already holds the summed [G | C] of all devices - kp_fit skips its Gram launch
@@ -63,6 +73,11 @@ struct kp_ctx {
   // MEAN kernel duration over them (timer 0), not just the last launch
   hipEvent_t ring[2 * 64] = {};
   int ring_pos = 0, ring_n = 0;
+  // ... a launch of the Gram queue serves ring_members fits, and a third event follows its partial reduction (timers 0 and 6
+  // are sums over the ring divided by the fits served)
+  hipEvent_t ring_red[64] = {};
+  int ring_members[64] = {};
+  bool ring_has_red[64] = {};
   bool solve_chained = false;   // set by a Gram launch that already made the solve stream wait for it
   int part_flip = 0;
   int reduce_timed_from = 1;   // evp index that marks the start of the last partial reduction
@@ -76,7 +91,7 @@ struct kp_ctx {
   int64_t hbm_bytes = 0;
   std::string name;
   mutable std::string err;
-  double timers[12] = {0};
+  double timers[14] = {0};            // (12: the group size of the Gram queue, 13: fits served by the launches of timer 7; kp_fit.hip)
   double gram_flops_per_pair = 0;
   // growable device workspaces
   void* ws[21] = {nullptr};     // slot 8: staging of the collectives, 9: rank-revealing solve, 10 / 11: Grams of the shadow dictionary of a dim_red fit, their half-transformed form
@@ -303,6 +318,9 @@ int kp_gram2_launch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s, d
 // picks the 4x4x4-MFMA kernel when the dictionary allows it, else the general kernel
 bool kp_gram3_applicable(const kp_basis* basis);
 int kp_gram3_launch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s, double* GC_dev);
+// n fits of one dictionary and snapshot count in one launch and one reduction; [G | C] of fit f at GC_dev + f 2 W^2 (kp_gram3.hip)
+bool kp_gram3_groupable(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s);
+int kp_gram3_launch_group(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* const* ss, int n, double* GC_dev);
 bool kp_gram_congruence_applicable(const kp_basis* basis);
 int kp_gram_congruence_launch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s, double* GC_dev);
 bool kp_gram3_linear_applicable(const kp_basis* basis);
@@ -336,6 +354,9 @@ int kp_pivchol_solve_dev(kp_ctx* ctx, const double* G_dev, const double* C_dev, 
 int kp_comm_allreduce_dev(kp_ctx* ctx, double* buf_dev, size_t count, hipStream_t s);
 // queued (deferred) solves of the asynchronous pipeline are launched; nothing is waited for, no status is consumed (kp_fit.hip)
 int kp_flush_pending(kp_ctx* ctx);
+// the queued Gram launches of the asynchronous pipeline are launched (kp_fit.hip); a no-op when nothing is queued
+int kp_flush_grams(kp_ctx* ctx);
+int kp_gram_group_size();   // KP_GRAM_GROUP (read once); kp_timer_get(12) reports it
 int kp_snapshots_update_rows(kp_ctx* ctx, kp_snapshots* s, const double* alpha, const double* beta, const double* u, int64_t Ns, int64_t ld);
 int kp_ensure_gc(kp_ctx* ctx, int W);   // the context's [G | C] buffer for width W (kp_fit.hip)
 int kp_lift_dev(kp_ctx* ctx, const kp_basis* basis, int what, const double* dz, const double* du, int64_t rows, double* dout);

@@ -285,6 +285,10 @@ extern "C" int kp_snapshots_upload(kp_ctx* ctx, const double* alpha, const doubl
     return ctx ? ctx->fail(KP_ERR_ARG, "kp_snapshots_upload: bad argument") : KP_ERR_ARG;
   *out = nullptr;
   KP_HIP(ctx, hipSetDevice(ctx->device));
+  {   // queued Gram launches go first, whichever objects they read: readers and refills keep the order they were issued in
+    int rc = kp_flush_grams(ctx);
+    if (rc) return rc;
+  }
   std::unique_ptr<kp_snapshots, int (*)(kp_snapshots*)> s(new kp_snapshots(), kp_snapshots_destroy);
   s->ctx = ctx;
   s->nzeta = nzeta;
@@ -314,6 +318,10 @@ int kp_snapshots_update_rows(kp_ctx* ctx, kp_snapshots* s, const double* alpha, 
   if (!ctx || !s || s->ctx != ctx || Ns < 0 || (Ns > 0 && (!alpha || !beta || (s->m > 0 && !u))))
     return ctx ? ctx->fail(KP_ERR_ARG, "kp_snapshots_update: bad argument") : KP_ERR_ARG;
   KP_HIP(ctx, hipSetDevice(ctx->device));
+  {   // (as kp_snapshots_upload: ANY object of the context, not only a queued one)
+    int rc = kp_flush_grams(ctx);
+    if (rc) return rc;
+  }
   bool fresh = false;
   if (Ns > s->cap_rows) {                            // grow: the old arrays must be idle before they are freed
     // idle the device WITHOUT consuming the deferred status of earlier fits (a NOT_SPD of a queued fit belongs to the
@@ -345,6 +353,7 @@ extern "C" int kp_snapshots_destroy(kp_snapshots* s) {
   if (!s) return KP_OK;
   if (s->ctx) {
     (void)hipSetDevice(s->ctx->device);
+    (void)kp_flush_grams(s->ctx);
     if (s->dma_pending && s->ev_ready) (void)hipEventSynchronize(s->ev_ready);
     if (s->read_pending && s->ev_read) (void)hipEventSynchronize(s->ev_read);
   }
