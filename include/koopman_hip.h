@@ -51,7 +51,13 @@ int kp_device_info(const kp_ctx* ctx, char* name, int name_len, int* num_cu, int
  * After a run of pipelined fits (kp_fit with K_out == NULL) timer 0 is the MEAN duration of the last (up to 64) Gram
  * launches and which = 7 the number of launches in that mean.  which = 8: the first (widest) product G [K_1 ... K_nv] of the
  * most recent lasso batch, 9: its number of columns (kp_symm_gemm2_kernel: the FISTA iteration's product); 10: flop per snapshot pair the most recent
- * fused lift+Gram launch EXECUTES on the matrix pipe (padding and, for dim_red dictionaries, the projection included); 11: host
+ * fused lift+Gram launch EXECUTES on the matrix pipe (padding and, for dim_red dictionaries, the projection included) - of the plan
+ * THAT launch ran.  The Kronecker kernel (bilinear dictionaries) has two plans for a dictionary of pure monomials: the circulant half
+ * of psi_x psi_x' and, where it saves a whole workgroup per snapshot split, a COVER of its distinct monomial products (W = 336:
+ * 24 x 6 x 10 x 128 = 184 320 against 28 x 6 x 10 x 128 = 215 040).  Pipelined fits (kp_fit with K_out == NULL: the Gram queue and
+ * its immediate dispatch) run the cover plan and report its count; kp_fit_gram, the synchronous kp_fit, kp_fit_sharded, kp_multi_*
+ * and the lasso paths run the circulant plan and report that.  Environment variable KP_GRAM3_COVER (read once): 0 - the circulant
+ * plan everywhere; 2 - the cover plan in every launch of such a dictionary, kp_fit_gram included (tests and A/B runs only).  11: host
  * milliseconds the most recent lasso batch spent in the regularisation-path homotopy (0: the projected-gradient iteration
  * finished every value; kp_fit_lasso below); 12: how many pipelined fits (kp_fit with K_out == NULL) of one dictionary and snapshot
  * count may share one Gram launch and one partial reduction (environment variable KP_GRAM_GROUP, read once; 1: none do) - timers 0

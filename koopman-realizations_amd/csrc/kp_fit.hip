@@ -1009,7 +1009,7 @@ static int solve_batch_size() {
 
 // Fits per Gram launch of the deferred-solve pipeline: KP_GRAM_GROUP (read once; 1: every fit is launched at once, on its own)
 int kp_gram_group_size() {
-  static const int v = [] { const char* e = getenv("KP_GRAM_GROUP"); return e ? std::min(KP_GRAM_GROUP_MAX, std::max(1, atoi(e))) : 8; }();   // (2 / 4 / 8 measured: DESIGN 6)
+  static const int v = [] { const char* e = getenv("KP_GRAM_GROUP"); return e ? std::min(KP_GRAM_GROUP_MAX, std::max(1, atoi(e))) : 5; }();   // (5 / 6 / 7 / 8 measured with the cover plan's six workgroups per split - 85 split units: 17 per fit fill 510 of 512 slots - DESIGN 6.2; 2 / 4 / 8 before it: 6.1)
   return v;
 }
 
@@ -1147,7 +1147,7 @@ extern "C" int kp_fit(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* sn
       ctx->reserve_cus = 0;
       ctx->reduce_stream = nullptr;
       ctx->ring_timing = true;
-      rc = kp_gram_dispatch(ctx, basis, snaps, GCs);
+      rc = kp_gram_dispatch(ctx, basis, snaps, GCs, true);           // (a fit too long to share a launch: the same plan as the queue's)
       ctx->ring_timing = false;
       if (rc) return rc;
       ++ctx->pend_solves;

@@ -79,6 +79,7 @@
 #define LDS3_GAUSS_DOUBLES (GAUSSMAX3 * GNZMAX3)
 
 #include "kp_gram3_args.h"
+#include "kp_gram3_cover.h"
 
 // the constant row of the in-loop power table "loads" its 1.0 like the raw rows load their values (kp_gram3_kernel, INL); not
 // `const`: a pointer that may be this or a kernel argument must stay a GLOBAL pointer (constant address space: flat loads)
@@ -689,9 +690,13 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
 // with four loads in flight; every order is fixed: bitwise reproducible.
 // blockIdx.y = fit of a group launch (kp_gram3_kernel, GRP): it sums that fit's nsplit splits - the global splits
 // [y nsplit, (y + 1) nsplit) - into that fit's [G | C] slot, 2 W^2 doubles behind the previous one.
+// dst_off != nullptr (cover plan, kp_gram3_cover.h): an element of an S block is written to every entry (i <= j) of psi_x psi_x'
+// whose monomial it is the designated source of - dst[dst_off[e] .. dst_off[e + 1]) of element e = ((job NQ + q) 4 + B slot) 16 +
+// 4 row + column - with the same four stores per entry; an element that is nobody's source writes nothing.  T blocks as ever.
 __global__ __launch_bounds__(1024) void kp_gram3_reduce_kernel(const double* __restrict__ part, int nsplit, int njobs, int NQ, int NWT,
                                                               int BM, const uint32_t* __restrict__ desc, int G4, int N, int W,
-                                                              double* __restrict__ G, double* __restrict__ C, int tup) {
+                                                              double* __restrict__ G, double* __restrict__ C, int tup,
+                                                              const uint32_t* __restrict__ dst_off, const uint32_t* __restrict__ dst) {
   const int idx = blockIdx.x;                 // (job*NQ + q)*NWT + w
   int w = idx % NWT;
   const int jq = idx / NWT, q = jq % NQ, job = jq / NQ;
@@ -733,7 +738,17 @@ __global__ __launch_bounds__(1024) void kp_gram3_reduce_kernel(const double* __r
     }
   const int ia = 4 * ga + (l >> 4);
   if (ia >= N) return;
-  if (gb < G4) {                              // S block: psi_x' psi_x  ->  G (symmetric)
+  if (gb < G4 && dst_off) {                   // S block of a cover plan: by monomial
+    const int e = (jq * 4 + gsel) * 16 + (l >> 4) * 4 + (l & 3);
+    for (uint32_t k = dst_off[e]; k < dst_off[e + 1]; ++k) {
+      const uint32_t d = dst[k];
+      const size_t di = d & 0xffffu, dj = d >> 16;
+      const size_t r1 = (size_t)wa * N + di, c1 = (size_t)wb * N + dj;
+      const size_t r2 = (size_t)wb * N + di, c2 = (size_t)wa * N + dj;
+      G[c1 * W + r1] = s; G[r1 * W + c1] = s;
+      G[c2 * W + r2] = s; G[r2 * W + c2] = s;
+    }
+  } else if (gb < G4) {                       // S block: psi_x' psi_x  ->  G (symmetric)
     const int jb = 4 * gb + (l & 3);
     if (jb >= N) return;
     if (ga == gb && ia > jb) return;          // diagonal block: keep the upper half, mirror below (exact symmetry)
@@ -753,78 +768,46 @@ struct kp_gram3_plan {
   int G4 = 0, nq = 0, njobs = 0, nsuper = 0;
   int wpw = 4;               // waves (jobs) per workgroup: 4 (kp_gram3_kernel) or 8 (kp_gram6_kernel, one workgroup per CU)
   uint32_t* desc = nullptr;  // device
+  // cover plan (kp_gram3_cover.h): the reduction's destination lists, device; nullptr in a circulant plan
+  uint32_t* dst_off = nullptr;
+  uint32_t* dst = nullptr;
+  // the circulant plan of a dictionary owns its cover plan, built on first use (gram3_cover_plan); nullptr: none is kept
+  kp_gram3_plan* cover = nullptr;
+  bool cover_tried = false;
 };
 
 void kp_gram3_plan_free(kp_gram3_plan* p) {
   if (!p) return;
+  kp_gram3_plan_free(p->cover);
   if (p->desc) (void)hipFree(p->desc);
+  if (p->dst_off) (void)hipFree(p->dst_off);
+  if (p->dst) (void)hipFree(p->dst);
   delete p;
+}
+
+static hipError_t plan3_upload(uint32_t** dev, const std::vector<uint32_t>& host) {
+  hipError_t e = hipMalloc((void**)dev, std::max<size_t>(host.size(), 1) * 4);
+  if (e == hipSuccess && !host.empty()) e = hipMemcpy(*dev, host.data(), host.size() * 4, hipMemcpyHostToDevice);
+  return e;
 }
 
 // Row g of psi_x (one 4-column group) is paired with: its circulant half of the psi_x groups
 // (g, g+1, ..., g+floor(G4/2) mod G4; antipodal pairs once) and all G4 groups of psi_y.
 // All quads (A group, 4 B groups) of all rows form one list; a job (one wave) is nq CONSECUTIVE quads,
-// so it spans at most two A groups when nq <= quads per row, and whole workgroups (4 jobs) fill evenly.
+// so it spans at most two A groups when nq <= quads per row, and whole workgroups (4 jobs) fill evenly (gram3_pack_rows).
 static int make_plan3(kp_ctx* ctx, int N, int nwt, int nq_cap, kp_gram3_plan** out, int wpw = 4, int nq_force = 0) {
   kp_gram3_plan* p = new kp_gram3_plan();
   p->wpw = wpw;
   const int G4 = (N + 3) / 4;
   p->G4 = G4;
-  const int ZG = 2 * G4;
-  std::vector<std::vector<int>> rows(G4);
-  for (int g = 0; g < G4; ++g) {
-    for (int d = 0; d <= G4 / 2; ++d) {
-      if (d > 0 && 2 * d == G4 && g >= G4 / 2) continue;
-      rows[g].push_back((g + d) % G4);
-    }
-    for (int h = 0; h < G4; ++h) rows[g].push_back(G4 + h);
-  }
   size_t maxq = 0;
-  for (auto& r : rows) maxq = std::max(maxq, (r.size() + 3) / 4);
-  std::vector<std::pair<int, uint32_t>> quads;
-  for (int g = 0; g < G4; ++g) {
-    const size_t nquads = (rows[g].size() + 3) / 4;
-    for (size_t q = 0; q < nquads; ++q) {
-      uint32_t packed = 0;
-      for (int k = 0; k < 4; ++k) {
-        size_t idx = q * 4 + k;
-        int gb = idx < rows[g].size() ? rows[g][idx] : ZG;
-        packed |= (uint32_t)gb << (8 * k);
-      }
-      quads.push_back({g, packed});
-    }
-  }
-  const int TQ = (int)quads.size();
-  // cost ~ waves x (MFMA cycles of nq quads over the two k-steps of a tile + the per-tile VALU share)
-  int nq = 1;
-  double best = 1e300;
-  constexpr int NQMAX = 6;   // 7 or 8 quads (140/160 accumulator registers) spill with the 256-register budget of 2 waves per SIMD
-  for (int c = 1; c <= std::min(NQMAX, nq_cap) && (size_t)c <= maxq; ++c) {
-    int waves = ((TQ + c - 1) / c + 3) / 4 * 4;
-    double cost = (double)waves * (c * nwt * 33.0 + 400.0);
-    if (cost < best) { best = cost; nq = c; }
-  }
-  if (nq_force > 0) nq = nq_force;
-  else if (const char* ov = getenv("KP_GRAM3_NQ")) {   // tuning override
-    int v = atoi(ov);
-    if (v >= 1 && v <= std::min(NQMAX, nq_cap) && (size_t)v <= maxq) nq = v;
-  }
-  p->nq = nq;
-  std::vector<uint32_t> desc;
-  int njobs = 0;
-  const uint32_t zq = (uint32_t)ZG * 0x01010101u;
-  for (int q0 = 0; q0 < TQ || njobs % wpw; q0 += nq) {
-    int a0 = q0 < TQ ? quads[q0].first : 0, a1 = a0, qs = nq;
-    for (int q = 0; q < nq; ++q)
-      if (q0 + q < TQ && quads[q0 + q].first != a0) { a1 = quads[q0 + q].first; qs = q; break; }
-    desc.push_back((uint32_t)a0 | ((uint32_t)a1 << 8) | ((uint32_t)qs << 16));
-    for (int q = 0; q < nq; ++q) desc.push_back(q0 + q < TQ ? quads[q0 + q].second : zq);
-    ++njobs;
-  }
-  p->njobs = njobs;
-  p->nsuper = njobs / wpw;
-  hipError_t e = hipMalloc((void**)&p->desc, desc.size() * 4);
-  if (e == hipSuccess) e = hipMemcpy(p->desc, desc.data(), desc.size() * 4, hipMemcpyHostToDevice);
+  const std::vector<std::vector<int>> rows = gram3_circulant_rows(G4, &maxq);
+  Gram3JobsHost jobs;
+  gram3_pack_rows(rows, G4, nwt, nq_cap, maxq, wpw, nq_force, &jobs);     // (quads, quads per job, job list: kp_gram3_cover.h)
+  p->nq = jobs.nq;
+  p->njobs = jobs.njobs;
+  p->nsuper = jobs.njobs / wpw;
+  hipError_t e = plan3_upload(&p->desc, jobs.desc);
   if (e != hipSuccess) {
     kp_gram3_plan_free(p);
     return ctx->fail(KP_ERR_HIP, std::string("kp_fit_gram: plan upload: ") + hipGetErrorString(e));
@@ -948,6 +931,62 @@ static int gram3_plan(kp_ctx* ctx, kp_basis* basis) {
             : make_plan3(ctx, N, NWT, b.k_pcs > 0 ? 4 : gram3_ext(basis) ? ext_cap : 6, &basis->plan3);     // (one plan serves both forms of a dim_red / fourier / gaussian fit)
 }
 
+// KP_GRAM3_COVER (read once): 0 - no launch takes a cover plan; unset or 1 - the launches of kp_fit's deferred-solve branch do
+// (the Gram queue of the pipelined fits and its immediate dispatch: kp_gram3_launch_group, kp_gram3_launch's `cover`); 2 - every launch of a qualifying dictionary,
+// kp_fit_gram included (tests and A/B runs only)
+static int gram3_cover_mode() {
+  static const int v = [] { const char* e = getenv("KP_GRAM3_COVER"); return e ? std::min(2, std::max(0, atoi(e))) : 1; }();
+  return v;
+}
+
+// The dictionary's cover plan (kp_gram3_cover.h), built on first use: for the in-kernel-lift monomial form with four-wave
+// workgroups only - every column a pure monomial, no projection, no fourier / gaussian table entries - and KEPT only when it has
+// fewer jobs (whole workgroups) than the circulant plan and passes its own coverage check on the host.  *out = nullptr: this
+// dictionary runs the circulant plan everywhere.
+static int gram3_cover_plan(kp_ctx* ctx, kp_basis* basis, kp_gram3_plan** out) {
+  kp_gram3_plan& circ = *basis->plan3;
+  *out = nullptr;
+  if (!circ.cover_tried) {
+    circ.cover_tried = true;
+    const BasisDev& b = basis->dev;
+    const int N = b.N, NWT = (b.m + 1) * (b.m + 2) / 2;
+    if (circ.wpw != 4 || b.k_pcs != 0 || gram3_ext(basis) || !basis->fast || b.nfull != N || (int)basis->h_recipes.size() != N) return KP_OK;
+    Gram3CoverHost cov;
+    if (!gram3_cover_build(basis->h_recipes.data(), N, basis->pow_depth, NWT, 6, circ.wpw, &cov) || cov.jobs.njobs >= circ.njobs) return KP_OK;
+    kp_gram3_plan* p = new kp_gram3_plan();
+    p->G4 = circ.G4;
+    p->nq = cov.jobs.nq;
+    p->njobs = cov.jobs.njobs;
+    p->nsuper = cov.jobs.njobs / circ.wpw;
+    p->cover_tried = true;
+    hipError_t e = plan3_upload(&p->desc, cov.jobs.desc);
+    if (e == hipSuccess) e = plan3_upload(&p->dst_off, cov.dst_off);
+    if (e == hipSuccess) e = plan3_upload(&p->dst, cov.dst);
+    if (e != hipSuccess) {
+      kp_gram3_plan_free(p);
+      circ.cover_tried = false;
+      return ctx->fail(KP_ERR_HIP, std::string("kp_fit_gram: plan upload: ") + hipGetErrorString(e));
+    }
+    circ.cover = p;
+  }
+  *out = circ.cover;
+  return KP_OK;
+}
+
+// the plan a launch runs: the dictionary's circulant plan, or its cover plan where the caller's path takes one and one is kept
+static int gram3_plan_for(kp_ctx* ctx, kp_basis* basis, bool deferred, kp_gram3_plan** out) {
+  int rc = gram3_plan(ctx, basis);
+  if (rc) return rc;
+  *out = basis->plan3;
+  if (gram3_cover_mode() == 2 || (gram3_cover_mode() == 1 && deferred)) {
+    kp_gram3_plan* cov = nullptr;
+    rc = gram3_cover_plan(ctx, basis, &cov);
+    if (rc) return rc;
+    if (cov) *out = cov;
+  }
+  return KP_OK;
+}
+
 // workgroup slots of the chip for this plan's kernel
 static int64_t gram3_slots(const kp_ctx* ctx, const kp_gram3_plan& plan, int* ncu_out = nullptr, int* wgpcu_out = nullptr) {
   int ncu = ctx->num_cu > 0 ? ctx->num_cu : 256;
@@ -970,16 +1009,17 @@ bool kp_gram3_groupable(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapshots
   kp_basis* basis = const_cast<kp_basis*>(basis_c);
   const BasisDev& b = basis->dev;
   if (!(kp_gram3_applicable(basis) && b.k_pcs == 0 && !gram3_ext(basis) && !gram6_on() && s->nzeta == b.nzeta && s->m == b.m)) return false;
-  if (gram3_plan(ctx, basis) != KP_OK || basis->plan3->wpw == 8) return false;      // (a plan that cannot be built: the immediate dispatch reports it)
+  kp_gram3_plan* plan = nullptr;                 // (the plan the queue's launch will run: kp_gram3_launch_group)
+  if (gram3_plan_for(ctx, basis, true, &plan) != KP_OK || plan->wpw == 8) return false;      // (a plan that cannot be built: the immediate dispatch reports it)
   static const int64_t max_kps = [] { const char* e = getenv("KP_GRAM_GROUP_MAX_KPS"); return e ? (int64_t)atoll(e) : (int64_t)512; }();
-  const int64_t ktiles = (s->Ns + KT3 - 1) / KT3, nsplit = std::max<int64_t>(1, gram3_slots(ctx, *basis->plan3) / basis->plan3->nsuper);
+  const int64_t ktiles = (s->Ns + KT3 - 1) / KT3, nsplit = std::max<int64_t>(1, gram3_slots(ctx, *plan) / plan->nsuper);
   return (ktiles + nsplit - 1) / nsplit < max_kps;
 }
 
 // ss[0 .. n): the snapshot objects of n fits of one dictionary and ONE snapshot count (n > 1: kp_gram3_groupable); their [G | C]
 // pairs go to GC_dev + f 2 W^2.  The launch is dealt over the fits: nsplit_fit = max(1, (slots / nsuper) / n) splits each.  n = 1
 // is the launch of a single fit, bit for bit.
-static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapshots* const* ss, int n, double* GC_dev) {
+static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapshots* const* ss, int n, double* GC_dev, bool cover) {
   kp_basis* basis = const_cast<kp_basis*>(basis_c);
   const BasisDev& b = basis->dev;
   const kp_snapshots* s = ss[0];
@@ -988,11 +1028,12 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
     if (ss[f]->nzeta != b.nzeta || ss[f]->m != b.m || ss[f]->Ns != s->Ns) return ctx->fail(KP_ERR_ARG, "kp_fit_gram: snapshot/basis dimension mismatch");
   const int W = b.W, N = b.N;
   const int BM = b.m, NWT = (BM + 1) * (BM + 2) / 2;
+  kp_gram3_plan* planp = nullptr;
   {
-    int rc = gram3_plan(ctx, basis);
+    int rc = gram3_plan_for(ctx, basis, cover, &planp);
     if (rc) return rc;
   }
-  kp_gram3_plan& plan = *basis->plan3;
+  kp_gram3_plan& plan = *planp;
   const int nfull4 = (b.nfull + 3) / 4 * 4;
   const bool ext = gram3_ext(basis);
   
@@ -1009,7 +1050,17 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   const size_t part_bytes = ((size_t)n * nsplit * per_split * 8 + 255) & ~(size_t)255;
   // sized for the largest split count of this dictionary at once: a workspace that grows with the snapshot count would put
   // a hipFree + hipMalloc of ~80 MB (17 ms, and a device synchronisation) into the first large fit of a running pipeline
-  const size_t part_max = ((size_t)std::max<int64_t>((int64_t)n * nsplit, (int64_t)ncu * wg_per_cu / plan.nsuper) * per_split * 8 + 255) & ~(size_t)255;
+  // (... and for both plans of the dictionary, the cover plan built now if it has one: synchronous and pipelined fits of it
+  // may alternate, whichever comes first)
+  if (gram3_cover_mode() != 0) {
+    kp_gram3_plan* cov = nullptr;
+    int rc = gram3_cover_plan(ctx, basis, &cov);
+    if (rc) return rc;
+  }
+  size_t part_max = ((size_t)std::max<int64_t>((int64_t)n * nsplit, (int64_t)ncu * wg_per_cu / plan.nsuper) * per_split * 8 + 255) & ~(size_t)255;
+  for (const kp_gram3_plan* o : {(const kp_gram3_plan*)basis->plan3, (const kp_gram3_plan*)basis->plan3->cover})
+    if (o && o != &plan)
+      part_max = std::max(part_max, ((size_t)((int64_t)ncu * wg_per_cu / o->nsuper) * o->njobs * o->nq * NWT * 64 * 8 + 255) & ~(size_t)255);
   char* part_base = (char*)ctx->workspace(4, part_max * (ctx->reduce_stream ? 2 : 1));
   if (!part_base) return ctx->fail(KP_ERR_HIP, "kp_fit_gram: out of device memory");
   double* part = (double*)(part_base + (ctx->reduce_stream ? (size_t)ctx->part_flip * part_bytes : 0));
@@ -1120,22 +1171,22 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   }
   ctx->reduce_timed_from = ctx->reduce_stream ? 4 : 1;
   hipLaunchKernelGGL(kp_gram3_reduce_kernel, dim3(plan.njobs * plan.nq * NWT, n), dim3(nsplit >= 128 ? 1024 : nsplit >= 32 ? 512 : 256), 0, rs, part, nsplit, plan.njobs,
-                     plan.nq, NWT, BM, plan.desc, plan.G4, N, W, GC_dev, GC_dev + (size_t)W * W, plan.wpw != 8 && gram3_tup(BM) ? 1 : 0);
+                     plan.nq, NWT, BM, plan.desc, plan.G4, N, W, GC_dev, GC_dev + (size_t)W * W, plan.wpw != 8 && gram3_tup(BM) ? 1 : 0, plan.dst_off, plan.dst);
   KP_HIP(ctx, hipGetLastError());
   if (ev_red) KP_HIP(ctx, hipEventRecord(ev_red, rs));
   if (!pipelined) KP_HIP(ctx, hipEventRecord(ctx->ev1, rs));
   if (!ctx->ring_timing) KP_HIP(ctx, hipEventRecord(ctx->evp[2], rs));
   ctx->gram_flops_per_pair = (double)W * (W + 1) + 2.0 * W * W;
-  // executed on the matrix pipe per pair (timer 10): jobs (padding included) x quads x weights MFMAs per 4 snapshots, 512 flop
+  // executed on the matrix pipe per pair (timer 10), of the plan THIS launch ran: jobs (padding included) x quads x weights MFMAs per 4 snapshots, 512 flop
   // each; dim_red: + the projection pcs' psi of every workgroup of a split (2 x nfull4 / 4 MFMAs per wave and tile)
   ctx->timers[10] = (double)plan.njobs * plan.nq * NWT * 128.0 + (b.k_pcs > 0 && !pre ? (double)plan.nsuper * nfull4 * 128.0 : 0.0);
   return KP_OK;
 }
 
-int kp_gram3_launch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s, double* GC_dev) { return gram3_launch_n(ctx, basis, &s, 1, GC_dev); }
+int kp_gram3_launch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s, double* GC_dev, bool cover) { return gram3_launch_n(ctx, basis, &s, 1, GC_dev, cover); }
 
 int kp_gram3_launch_group(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* const* ss, int n, double* GC_dev) {
-  return gram3_launch_n(ctx, basis, ss, n, GC_dev);
+  return gram3_launch_n(ctx, basis, ss, n, GC_dev, true);
 }
 
 

@@ -317,8 +317,10 @@ bool kp_gram2_applicable(const kp_basis* basis);
 int kp_gram2_launch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s, double* GC_dev);
 // picks the 4x4x4-MFMA kernel when the dictionary allows it, else the general kernel
 bool kp_gram3_applicable(const kp_basis* basis);
-int kp_gram3_launch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s, double* GC_dev);
-// n fits of one dictionary and snapshot count in one launch and one reduction; [G | C] of fit f at GC_dev + f 2 W^2 (kp_gram3.hip)
+// cover: the caller is kp_fit's deferred-solve branch - the launch takes the dictionary's cover plan where it has one (kp_gram3_cover.h)
+int kp_gram3_launch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s, double* GC_dev, bool cover = false);
+// n fits of one dictionary and snapshot count in one launch and one reduction; [G | C] of fit f at GC_dev + f 2 W^2 (kp_gram3.hip).
+// Both are the Gram queue's (kp_fit.hip): they plan with the dictionary's cover plan where it has one
 bool kp_gram3_groupable(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s);
 int kp_gram3_launch_group(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* const* ss, int n, double* GC_dev);
 bool kp_gram_congruence_applicable(const kp_basis* basis);
@@ -328,12 +330,12 @@ int kp_gram3_linear_launch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshot
 void kp_gram3_shadow_free(kp_basis* basis);
 bool kp_gram5_applicable(const kp_basis* basis);
 int kp_gram5_launch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s, double* GC_dev);
-inline int kp_gram_dispatch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s, double* GC_dev) {
+inline int kp_gram_dispatch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s, double* GC_dev, bool cover = false) {
   if (s->Ns > 0 && (!s->alpha || !s->beta || (s->m > 0 && !s->u)))    // an object whose refill failed part-way (kp_snapshots_update)
     return ctx->fail(KP_ERR_ARG, "kp_fit: the snapshot object holds no device arrays (a failed kp_snapshots_update?)");
   ctx->reduce_timed_from = 1;
   KP_HIP(ctx, kp_snaps_acquire(s, ctx->stream));
-  const int rc = kp_gram3_applicable(basis)   ? kp_gram3_launch(ctx, basis, s, GC_dev)
+  const int rc = kp_gram3_applicable(basis)   ? kp_gram3_launch(ctx, basis, s, GC_dev, cover)
                  : kp_gram_congruence_applicable(basis) ? kp_gram_congruence_launch(ctx, basis, s, GC_dev)
                  : kp_gram3_linear_applicable(basis) ? kp_gram3_linear_launch(ctx, basis, s, GC_dev)
                  : kp_gram5_applicable(basis) ? kp_gram5_launch(ctx, basis, s, GC_dev)
