@@ -65,7 +65,12 @@ int kp_device_info(const kp_ctx* ctx, char* name, int name_len, int* num_cu, int
  * number of fits served by the launches that timer 7 counts (timer 7 itself stays the number of launches).  A fit of a group of n sums its snapshots
  * over 1 / n of the splits of a lone launch - the same terms in another fixed order - so the last bits of a pipelined K depend on
  * how many fits were queued with it (5e-14 at W = 336 between a member of a group of 8 and of 4); only fits of fewer than 512
- * snapshot tiles per split (about 3e5 pairs at W = 336) are grouped. */
+ * snapshot tiles per split (about 3e5 pairs at W = 336) are grouped.  14: not a time - which kernels the most recent
+ * kp_sweep_eval / kp_sweep_eval_nested ran, as the decimal code 1000 G + 100 F + 10 U + R.  G, the Gram pass: 1 kp_traj_gram_kernel,
+ * 2 kp_traj_gram_cols_kernel, 3 kp_traj_gram_mfma_kernel with a compile-time shape, 4 the same with a run-time shape, 5
+ * kp_small_fit_kernel with power-table recipes (kp_sweep_eval), 6 the same without.  F: the factors per operand value of the mfma
+ * kernel (its template argument), 0 for every other kernel.  U: 1 if the mfma kernel keeps the bilinear input products in its
+ * table (UPRO).  R, the rollout: 1 kp_sweep_rollout4_kernel, 2 kp_sweep_rollout_nested_kernel, 3 kp_sweep_rollout_kernel. */
 int kp_timer_get(const kp_ctx* ctx, int which, double* ms);
 /* Device pointer + byte size of the library stream's raw handle, for profilers/benchmarks
  * that want to bracket work with their own HIP events: returns hipStream_t as void*. */
@@ -270,7 +275,8 @@ int kp_sweep_eval(kp_ctx* ctx, const kp_traj* traj, const kp_basis* basis, doubl
  * :47-143 loops degree by degree; def_polyLift orders monomials by total degree, Ksysid.m:645-648, so the degree-j
  * dictionary is a column subset of the degree-D one and its Grams are sub-blocks).  `basis` is the dictionary of the
  * highest degree.  The Grams are accumulated in a Chebyshev internal basis (data are scaled to [-1, 1]) and mapped back
- * exactly (K_m = T^-1 K_c T): QR-level accuracy of K without a refinement sweep.  err_out: n_deg x nb x n
+ * exactly (K_m = T^-1 K_c T): QR-level accuracy of K without a refinement sweep.  A sparse table that lacks a
+ * term of the Chebyshev expansion of one of its monomials ([x, x^9, 1]) is not spanned by that basis and keeps its monomials.  err_out: n_deg x nb x n
  * (degree-major); status_out (n_deg x nb, may be NULL).  kp_sweep_nested_get_K fetches the K matrices (monomial basis,
  * W_j x W_j each) of one degree of the most recent call (parity checks). */
 int kp_sweep_eval_nested(kp_ctx* ctx, const kp_traj* traj, const kp_basis* basis, double lasso, int n_deg, double* err_out,

@@ -795,6 +795,7 @@ extern "C" int kp_sweep_eval(kp_ctx* ctx, const kp_traj* traj, const kp_basis* b
   }
   hipLaunchKernelGGL(kp_sweep_rollout_kernel, dim3(nb), dim3(64), 0, s, b, dK, dA, dB, traj->Yv, traj->Uv, traj->sc, traj->Tv, dS, dE);
   KP_HIP(ctx, hipGetLastError());
+  ctx->timers[14] = (use_rec ? 5000.0 : 6000.0) + 3.0;   // kp_small_fit_kernel with / without recipes, kp_sweep_rollout_kernel
   KP_HIP(ctx, hipMemcpyAsync(err_out, dE, (size_t)nb * n * 8, hipMemcpyDeviceToHost, s));
   if (K_out) KP_HIP(ctx, hipMemcpyAsync(K_out, dK, bW, hipMemcpyDeviceToHost, s));
   if (status_out) KP_HIP(ctx, hipMemcpyAsync(status_out, dS, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
@@ -971,7 +972,7 @@ __global__ __launch_bounds__(256) void kp_traj_gram_kernel(BasisDev b, const uin
 #define TGM_NV 4                                      // dictionary variables ([zeta] or [zeta; u]) this kernel takes
 template <int F, int DC, int NVC, bool UPRO>
 __global__ __launch_bounds__(256, 2) void kp_traj_gram_mfma_kernel(BasisDev b, const uint32_t* __restrict__ recipes, int D_rt, TrajView tv, int Ns,
-                                                                    double* __restrict__ Gout, double* __restrict__ Cout) {
+                                                                    int cheb, double* __restrict__ Gout, double* __restrict__ Cout) {
   extern __shared__ __align__(16) double sm[];
   const int nv = b.nvars, m = b.m, N = b.N, W = b.W, nz = b.nzeta;
   const int D = DC > 0 ? DC : D_rt;                   // DC: the table depth at compile time (the sweep's 13 / 6 / 4): unrolled fill
@@ -1086,14 +1087,14 @@ __global__ __launch_bounds__(256, 2) void kp_traj_gram_mfma_kernel(BasisDev b, c
 #pragma unroll
             for (int k = 0; k < DC; ++k) {
               put(k, q);
-              const double qn = x2 * q - qm;
+              const double qn = cheb ? x2 * q - qm : x * q;       // T_(k+1)(x) okf, or x^(k+1) okf for a sparse table
               qm = q;
               q = qn;
             }
           } else {
             for (int k = 0; k < D; ++k) {
               put(k, q);
-              const double qn = x2 * q - qm;
+              const double qn = cheb ? x2 * q - qm : x * q;       // T_(k+1)(x) okf, or x^(k+1) okf for a sparse table
               qm = q;
               q = qn;
             }
@@ -1778,13 +1779,34 @@ extern "C" int kp_sweep_eval_nested(kp_ctx* ctx, const kp_traj* traj, const kp_b
   cheb_table(dmax, s1);
   std::vector<SweepDeg> degs(n_deg);
   std::vector<ColDesc> cols_all((size_t)n_deg * 16, ColDesc{COL_CONST, 0, 0, 0});
-  for (int dj = 0; dj < n_deg; ++dj) {
-    const int j = dj + 1;
-    SweepDeg& d = degs[dj];
-    std::vector<int> psi;                            // columns of psi_D that make psi_j: degree <= j, then the constant
+  auto cols_of_degree = [&](int j) {                 // columns of psi_D that make psi_j: degree <= j, then the constant
+    std::vector<int> psi;
     for (int c = 0; c + 1 < Nmax; ++c)
       if (deg[c] <= j) psi.push_back(c);
     psi.push_back(Nmax - 1);
+    return psi;
+  };
+  // The Chebyshev internal basis spans psi_j only if, with a monomial, every product of T_b(x_v) in its expansion (b = a, a - 2,
+  // ...) is a column of psi_j too - true of the full tables of def_polyLift, not of a sparse one: [x, x^9, 1] against [T_1, T_9, 1]
+  // is another dictionary and gave another K.  Such tables keep the monomials as the internal basis (S = I).
+  bool cheb = true;
+  for (int dj = 0; dj < n_deg && cheb; ++dj) {
+    const std::vector<int> psi = cols_of_degree(dj + 1);
+    for (int r : psi) {
+      int terms = 1, hits = 0;
+      for (int v = 0; v < nv; ++v) terms *= ex[r][v] / 2 + 1;
+      for (int c : psi) {
+        bool hit = true;
+        for (int v = 0; v < nv; ++v) hit = hit && ex[c][v] <= ex[r][v] && ((ex[r][v] - ex[c][v]) & 1) == 0;
+        hits += hit ? 1 : 0;
+      }
+      if (hits != terms) cheb = false;
+    }
+  }
+  for (int dj = 0; dj < n_deg; ++dj) {
+    const int j = dj + 1;
+    SweepDeg& d = degs[dj];
+    const std::vector<int> psi = cols_of_degree(j);
     const int Nj = (int)psi.size();
     d.N = Nj;
     d.W = b.model_type == KP_MODEL_LINEAR ? Nj + m : b.model_type == KP_MODEL_BILINEAR ? Nj * (m + 1) : Nj;
@@ -1798,7 +1820,7 @@ extern "C" int kp_sweep_eval_nested(kp_ctx* ctx, const kp_traj* traj, const kp_b
           const int a = ex[psi[r]][v], bq = ex[psi[c]][v];
           p *= bq <= a ? (long double)s1[a][bq] : 0.0L;
         }
-        Sp[(size_t)r * Nj + c] = p;
+        Sp[(size_t)r * Nj + c] = cheb ? p : (r == c ? 1.0L : 0.0L);
       }
     std::vector<long double> Sf((size_t)256, 0.0L);
     for (int q = 0; q < 16; ++q) Sf[q * 16 + q] = 1.0L;
@@ -1881,6 +1903,7 @@ extern "C" int kp_sweep_eval_nested(kp_ctx* ctx, const kp_traj* traj, const kp_b
   // round 4: the sweep's own shapes (1 state, 1 input, canonical polynomial dictionary) with the row's columns in the table
   static const bool cols_off = getenv("KP_SWEEP_GRAM_V1") != nullptr;
   bool use_cols = false;
+  int code_g = 1, code_f = 0, code_u = 0;              // timer 14: which Gram kernel this call runs (koopman_hip.h)
   if (!cols_off && !gram_old && n == 1 && m == 1 && b.nzeta == 1 && b.k_pcs == 0 && tgc_canonical(basis, nv, Dp)) {
 #define KP_TGC(MT_, D_)                                                                                                           \
     {                                                                                                                             \
@@ -1890,6 +1913,7 @@ extern "C" int kp_sweep_eval_nested(kp_ctx* ctx, const kp_traj* traj, const kp_b
       KP_HIP(ctx, hipEventRecord(ctx->ev0, s));                                                                                   \
       hipLaunchKernelGGL((kp_traj_gram_cols_kernel<MT_, D_>), dim3(nb), dim3(256), lds_c, s, traj_view(traj), Ns, dGc, dCc);      \
       use_cols = true;                                                                                                            \
+      code_g = 2;                                                                                                                 \
       ctx->timers[10] = 26.0 * 512.0 / 16.0;   /* executed on the matrix pipe per pair: 10 + 16 MFMAs per 16 pairs */            \
     }
     if (b.model_type == KP_MODEL_LINEAR && Dp == 13) KP_TGC(KP_MODEL_LINEAR, 13)
@@ -1906,7 +1930,8 @@ extern "C" int kp_sweep_eval_nested(kp_ctx* ctx, const kp_traj* traj, const kp_b
       KP_HIP(ctx, kp_ensure_lds(tgm_lds, (const void*)kp_traj_gram_mfma_kernel<F_, DC_, NV_, UP_>, lds_m));                       \
       KP_HIP(ctx, hipEventRecord(ctx->ev0, s));                                                                                   \
       hipLaunchKernelGGL((kp_traj_gram_mfma_kernel<F_, DC_, NV_, UP_>), dim3(nb), dim3(256), lds_m, s, b,                         \
-                         (const uint32_t*)basis->d_recipes, Dp, traj_view(traj), Ns, dGc, dCc);                                   \
+                         (const uint32_t*)basis->d_recipes, Dp, traj_view(traj), Ns, cheb ? 1 : 0, dGc, dCc);                     \
+      code_g = (DC_) > 0 ? 3 : 4; code_f = F_; code_u = (UP_) ? 1 : 0;                                                            \
     }
     // the shapes of evaluate_rand_models.m (1-D systems: linear degree 13, bilinear 6, nonlinear 4) with the table depth and
     // the variable count at compile time; everything else with run-time values
@@ -1932,7 +1957,7 @@ extern "C" int kp_sweep_eval_nested(kp_ctx* ctx, const kp_traj* traj, const kp_b
     KP_HIP(ctx, kp_ensure_lds(tg_lds, (const void*)kp_traj_gram_kernel, lds));
     KP_HIP(ctx, hipEventRecord(ctx->ev0, s));
     hipLaunchKernelGGL(kp_traj_gram_kernel, dim3(nb), dim3(256), lds, s, b, (const uint32_t*)basis->d_recipes, Dp, basis->max_factors > 0 ? basis->max_factors : 1,
-                       traj_view(traj), Ns, 1, dGc, dCc);
+                       traj_view(traj), Ns, cheb ? 1 : 0, dGc, dCc);
   }
   KP_HIP(ctx, hipGetLastError());
   KP_HIP(ctx, hipEventRecord(ctx->ev1, s));
@@ -1969,6 +1994,7 @@ extern "C" int kp_sweep_eval_nested(kp_ctx* ctx, const kp_traj* traj, const kp_b
     hipLaunchKernelGGL(kp_sweep_rollout_nested_kernel, grid, dim3(64), 0, s, b, dT, dCols, nb, dK, b.model_type == KP_MODEL_LINEAR ? dA : nullptr,
                        b.model_type == KP_MODEL_LINEAR ? dB : nullptr, traj->Yv, traj->Uv, traj->Tv, dS, dE);
   KP_HIP(ctx, hipGetLastError());
+  ctx->timers[14] = 1000.0 * code_g + 100.0 * code_f + 10.0 * code_u + (rollout4 && n <= 4 ? 1.0 : 2.0);
   KP_HIP(ctx, hipMemcpyAsync(err_out, dE, (size_t)n_deg * nb * n * 8, hipMemcpyDeviceToHost, s));
   if (status_out) KP_HIP(ctx, hipMemcpyAsync(status_out, dS, (size_t)n_deg * nb * 4, hipMemcpyDeviceToHost, s));
   KP_HIP(ctx, hipStreamSynchronize(s));
