@@ -70,7 +70,11 @@ int kp_device_info(const kp_ctx* ctx, char* name, int name_len, int* num_cu, int
  * 2 kp_traj_gram_cols_kernel, 3 kp_traj_gram_mfma_kernel with a compile-time shape, 4 the same with a run-time shape, 5
  * kp_small_fit_kernel with power-table recipes (kp_sweep_eval), 6 the same without.  F: the factors per operand value of the mfma
  * kernel (its template argument), 0 for every other kernel.  U: 1 if the mfma kernel keeps the bilinear input products in its
- * table (UPRO).  R, the rollout: 1 kp_sweep_rollout4_kernel, 2 kp_sweep_rollout_nested_kernel, 3 kp_sweep_rollout_kernel. */
+ * table (UPRO).  R, the rollout: 1 kp_sweep_rollout4_kernel, 2 kp_sweep_rollout_nested_kernel, 3 kp_sweep_rollout_kernel.  15: not a time -
+ * how many jobs (waves per snapshot split) of the plan the most recent Kronecker Gram launch ran span two A groups of psi_x: such a
+ * wave weighs two A fragments per k-step.  Where the search finds one, the cover plan of a dictionary is its ONE-A-GROUP plan
+ * (every row of the plan one job, a few hub rows two: 0 here; the same job and flop count, timer 10); environment variable
+ * KP_GRAM3_ONEA=0 (read once) keeps the cover plan of consecutive quads (W = 336: 17 of 24 jobs) for A/B runs and tests. */
 int kp_timer_get(const kp_ctx* ctx, int which, double* ms);
 /* Device pointer + byte size of the library stream's raw handle, for profilers/benchmarks
  * that want to bracket work with their own HIP events: returns hipStream_t as void*. */

@@ -767,6 +767,7 @@ __global__ __launch_bounds__(1024) void kp_gram3_reduce_kernel(const double* __r
 struct kp_gram3_plan {
   int G4 = 0, nq = 0, njobs = 0, nsuper = 0;
   int wpw = 4;               // waves (jobs) per workgroup: 4 (kp_gram3_kernel) or 8 (kp_gram6_kernel, one workgroup per CU)
+  int two_group_jobs = 0;    // jobs that span two A groups: their waves weigh two A fragments per k-step (kp_timer_get(15))
   uint32_t* desc = nullptr;  // device
   // cover plan (kp_gram3_cover.h): the reduction's destination lists, device; nullptr in a circulant plan
   uint32_t* dst_off = nullptr;
@@ -807,6 +808,7 @@ static int make_plan3(kp_ctx* ctx, int N, int nwt, int nq_cap, kp_gram3_plan** o
   p->nq = jobs.nq;
   p->njobs = jobs.njobs;
   p->nsuper = jobs.njobs / wpw;
+  p->two_group_jobs = gram3_two_group_jobs(jobs);
   hipError_t e = plan3_upload(&p->desc, jobs.desc);
   if (e != hipSuccess) {
     kp_gram3_plan_free(p);
@@ -939,10 +941,20 @@ static int gram3_cover_mode() {
   return v;
 }
 
+// KP_GRAM3_ONEA=0 (read once): the cover plan of gram3_cover_build even where the dictionary has a one-A-group plan (A/B runs, tests)
+static bool gram3_onea_on() {
+  static const bool on = [] { const char* e = getenv("KP_GRAM3_ONEA"); return !e || atoi(e) != 0; }();
+  return on;
+}
+
 // The dictionary's cover plan (kp_gram3_cover.h), built on first use: for the in-kernel-lift monomial form with four-wave
 // workgroups only - every column a pure monomial, no projection, no fourier / gaussian table entries - and KEPT only when it has
 // fewer jobs (whole workgroups) than the circulant plan and passes its own coverage check on the host.  *out = nullptr: this
 // dictionary runs the circulant plan everywhere.
+// A kept cover plan is replaced by the dictionary's one-A-group plan (gram3_onea_build: same quads per job, no job spans two A
+// groups, so no wave weighs a second A fragment) where the search finds one with no more jobs; where it finds none, or with
+// KP_GRAM3_ONEA=0, the cover plan stays byte for byte what gram3_cover_build made.  The search costs ~35 ms of host time for
+// the headline dictionary, once per dictionary, here on its first pipelined fit.
 static int gram3_cover_plan(kp_ctx* ctx, kp_basis* basis, kp_gram3_plan** out) {
   kp_gram3_plan& circ = *basis->plan3;
   *out = nullptr;
@@ -953,8 +965,13 @@ static int gram3_cover_plan(kp_ctx* ctx, kp_basis* basis, kp_gram3_plan** out) {
     if (circ.wpw != 4 || b.k_pcs != 0 || gram3_ext(basis) || !basis->fast || b.nfull != N || (int)basis->h_recipes.size() != N) return KP_OK;
     Gram3CoverHost cov;
     if (!gram3_cover_build(basis->h_recipes.data(), N, basis->pow_depth, NWT, 6, circ.wpw, &cov) || cov.jobs.njobs >= circ.njobs) return KP_OK;
+    if (gram3_onea_on()) {
+      Gram3CoverHost one;
+      if (gram3_onea_build(basis->h_recipes.data(), N, basis->pow_depth, cov, &one) && one.jobs.nq == cov.jobs.nq && one.jobs.njobs <= cov.jobs.njobs) cov = std::move(one);
+    }
     kp_gram3_plan* p = new kp_gram3_plan();
     p->G4 = circ.G4;
+    p->two_group_jobs = gram3_two_group_jobs(cov.jobs);
     p->nq = cov.jobs.nq;
     p->njobs = cov.jobs.njobs;
     p->nsuper = cov.jobs.njobs / circ.wpw;
@@ -1180,6 +1197,7 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   // executed on the matrix pipe per pair (timer 10), of the plan THIS launch ran: jobs (padding included) x quads x weights MFMAs per 4 snapshots, 512 flop
   // each; dim_red: + the projection pcs' psi of every workgroup of a split (2 x nfull4 / 4 MFMAs per wave and tile)
   ctx->timers[10] = (double)plan.njobs * plan.nq * NWT * 128.0 + (b.k_pcs > 0 && !pre ? (double)plan.nsuper * nfull4 * 128.0 : 0.0);
+  ctx->timers[15] = (double)plan.two_group_jobs;   // jobs of this launch's plan that span two A groups (0: a one-A-group plan)
   return KP_OK;
 }
 
