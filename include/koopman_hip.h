@@ -74,7 +74,12 @@ int kp_device_info(const kp_ctx* ctx, char* name, int name_len, int* num_cu, int
  * how many jobs (waves per snapshot split) of the plan the most recent Kronecker Gram launch ran span two A groups of psi_x: such a
  * wave weighs two A fragments per k-step.  Where the search finds one, the cover plan of a dictionary is its ONE-A-GROUP plan
  * (every row of the plan one job, a few hub rows two: 0 here; the same job and flop count, timer 10); environment variable
- * KP_GRAM3_ONEA=0 (read once) keeps the cover plan of consecutive quads (W = 336: 17 of 24 jobs) for A/B runs and tests. */
+ * KP_GRAM3_ONEA=0 (read once) keeps the cover plan of consecutive quads (W = 336: 17 of 24 jobs) for A/B runs and tests.  16: not a
+ * time - how many power-table entries per raw value (x, x^2, ...) the in-loop table build of the most recent Kronecker Gram launch's
+ * kernel writes: 3 for a monomial dictionary without fourth powers and without a projection (its launches neither compute nor store
+ * the x^4 entry that nothing reads), 4 otherwise; 0 for the forms that build no table in the loop (prelifted dim_red tiles, fourier /
+ * gaussian entries, the eight-wave experiment).  The results do not depend on it, bit for bit; environment variable KP_GRAM3_POW3=0
+ * (read once) keeps four entries everywhere for A/B runs and tests. */
 int kp_timer_get(const kp_ctx* ctx, int which, double* ms);
 /* Device pointer + byte size of the library stream's raw handle, for profilers/benchmarks
  * that want to bracket work with their own HIP events: returns hipStream_t as void*. */

@@ -35,6 +35,11 @@
 // (147 spilled registers), the items with three real factors gathered in the last wave so that the others skip a read and a multiply (branches and the
 // scattered stores cost more), B operands 2 / 4 steps ahead and the raw load behind other steps (no difference), cbsz / abid
 // (they do not broadcast blocks on v_mfma_f64_4x4x4_4b: tools/mfma_bcast_probe.hip).
+// Later, on the one-A-group plan: a dictionary without fourth powers runs a form whose in-loop table build writes
+// three entries, not four (P3: 0.3068 -> 0.3044 ms per fit, kept).  Measured and NOT kept: the lift's jobs in an order built on
+// the host, every job of three real factors in lift step 0, so that steps 1 and 2 read two factors and multiply once - 4 v_mul_f64
+// and 2 ds_read_b128 less per wave and tile, but the compiler then reloads 5 spilled address registers inside every tile (none
+// before), behind the tile's raw load in the vmcnt order: 0.3068 -> 0.3127 ms.
 //
 // Replaces the per-row lift loop of Ksysid.get_Koopman (Ksysid.m:1030-1065) and the products
 // PxTPx, PxTPy (Ksysid.m:1114,1125) for model_type 'bilinear'.
@@ -92,9 +97,12 @@ __device__ double kp_gram3_ones[KT3] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
 // 40 (weight, group) blocks, bit for bit, with 5 weight multiplies per A group and k-step instead of 9 (nothing on the vector
 // pipe overlaps the f64 MFMA stream: each costs ~5.5 cycles of it) and 10 operand registers less; the price is a second
 // operand read per quad.  The weights sit in the 12 weight entries of a Psi row in tuple order (wslot), w_0 = 1 stored.
-template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool TUP = false>
+// P3 (the in-kernel-lift monomial form without a projection; dictionaries of powers <= 3): the in-loop table build writes x, x^2, x^3 and no
+// x^4 entry that nothing reads - a v_mul_f64 and a ds_write_b64 less per wave and tile.
+template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool TUP = false, bool P3 = false>
 __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
   constexpr int NWT = (BM + 1) * (BM + 2) / 2;
+  static_assert(!P3 || (!PCS && !EXT && !PRE), "three-entry table: the in-kernel-lift monomial form");
   static_assert(!TUP || NWT % 2 == 0, "paired weights: an even number of weights (m = 3: 10 = 5 tuples, m = 2: 6 = 3 tuples)");
   // TUP: weight w sits in slot 6 (w & 1) + (w >> 1) of the 12 weight entries of a Psi row (w_0 = 1 stored in slot 0): the five
   // weights a lane multiplies in - w_{2p+h}, p = 0..4, h = blk >> 1 - are contiguous and 16-byte aligned (two ds_read_b128 and a
@@ -349,14 +357,17 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
       const int64_t s_glob = (kt0 + tile) * KT3 + ld_s;
       if (s_glob >= a.Ns) xv = 0.0;
     }
-    const double x2 = xv * xv, x3 = x2 * xv, x4 = x2 * x2;
+    const double x2 = xv * xv, x3 = x2 * xv;
     const uint32_t tb_dst_b = tb_dst;                              // (an asm operand alone does not capture in a generic lambda)
     // (8-byte stores at immediate offsets from one address register: four entries 80 bytes apart, no ds_write2 pairs them without
     // an add; 0.3640 against 0.3659 ms for the compiler's stores.  Not counted by the compiler: see lds_store_barrier)
     asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(tb_dst_b), "v"(xv), "n"((BUF * POWBUF3) * 8) : "memory");
     asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(tb_dst_b), "v"(x2), "n"((BUF * POWBUF3 + PST3) * 8) : "memory");
     asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(tb_dst_b), "v"(x3), "n"((BUF * POWBUF3 + 2 * PST3) * 8) : "memory");
-    asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(tb_dst_b), "v"(x4), "n"((BUF * POWBUF3 + 3 * PST3) * 8) : "memory");
+    if constexpr (!P3) {   // (P3: no recipe holds a fourth power; the entry keeps the zeros of the one-time setup)
+      const double x4 = x2 * x2;
+      asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(tb_dst_b), "v"(x4), "n"((BUF * POWBUF3 + 3 * PST3) * 8) : "memory");
+    }
   };
   auto store_tb = [&](auto buf_c) __attribute__((always_inline)) { store_tb_v(buf_c, tb_v, tb_tile - 1); };
   // the first three tiles' raw values are requested HERE, in front of the one-time LDS setup and its barriers: the setup runs in
@@ -825,20 +836,24 @@ static bool gram3_tup(int bm) {
   return bm >= 2 && !off;              // (an even number of weights: m = 2 -> 6, m = 3 -> 10)
 }
 
-template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool TUP = false>
+template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool TUP = false, bool P3 = false>
 static hipError_t launch3c(const Gram3Args& a, int grid, size_t lds, hipStream_t st) {
   static KpLdsCache lds_cache;
   {
     const size_t lds_max = (size_t)(LDS3_DOUBLES + (PCS ? LDS3_PCS_DOUBLES : 0) + (EXT ? LDS3_GAUSS_DOUBLES : 0)) * sizeof(double);
-    hipError_t e = kp_ensure_lds(lds_cache, (const void*)kp_gram3_kernel<NQ, BM, PCS, EXT, PRE, TUP>, lds_max);
+    hipError_t e = kp_ensure_lds(lds_cache, (const void*)kp_gram3_kernel<NQ, BM, PCS, EXT, PRE, TUP, P3>, lds_max);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((kp_gram3_kernel<NQ, BM, PCS, EXT, PRE, TUP>), dim3(grid), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((kp_gram3_kernel<NQ, BM, PCS, EXT, PRE, TUP, P3>), dim3(grid), dim3(256), lds, st, a);
   return hipGetLastError();
 }
 
 template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false>
 static hipError_t launch3b(const Gram3Args& a, int grid, size_t lds, hipStream_t st) {
+  if constexpr (!PCS && !EXT && !PRE) {
+    // no fourth power in the dictionary: the three-entry table, in the default weight form (gram3_launch_n sets pow3 only there)
+    if (a.pow3) return launch3c<NQ, BM, false, false, false, (BM >= 2), true>(a, grid, lds, st);
+  }
   if constexpr (BM >= 2) {
     if (gram3_tup(BM)) return launch3c<NQ, BM, PCS, EXT, PRE, true>(a, grid, lds, st);
   }
@@ -990,6 +1005,12 @@ static int gram3_cover_plan(kp_ctx* ctx, kp_basis* basis, kp_gram3_plan** out) {
   return KP_OK;
 }
 
+// KP_GRAM3_POW3=0 (read once): the in-loop table build keeps its x^4 entry for every dictionary (A/B runs, tests)
+static bool gram3_pow3_on() {
+  static const bool on = [] { const char* e = getenv("KP_GRAM3_POW3"); return !e || atoi(e) != 0; }();
+  return on;
+}
+
 // the plan a launch runs: the dictionary's circulant plan, or its cover plan where the caller's path takes one and one is kept
 static int gram3_plan_for(kp_ctx* ctx, kp_basis* basis, bool deferred, kp_gram3_plan** out) {
   int rc = gram3_plan(ctx, basis);
@@ -1135,6 +1156,8 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   a.pre_rl = pre_rl;
   a.nsplit_fit = nsplit;
   for (int f = 0; f < n; ++f) a.grp[f] = Gram3Src{ss[f]->alpha, ss[f]->beta, ss[f]->u};
+  // the in-kernel-lift monomial form without a projection, in its default weight form: three table entries where no recipe reads a fourth
+  a.pow3 = !pre && b.k_pcs == 0 && !ext && plan.wpw == 4 && basis->pow_depth <= 3 && (BM < 2 || gram3_tup(BM)) && gram3_pow3_on();
   const int grid = plan.nsuper * nsplit * n;
   // every event record is a barrier packet the command processor works through between two Gram kernels: the
   // pipelined path keeps two (kernel start / end; the end also releases the reduction on the solve stream)
@@ -1197,6 +1220,8 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   // executed on the matrix pipe per pair (timer 10), of the plan THIS launch ran: jobs (padding included) x quads x weights MFMAs per 4 snapshots, 512 flop
   // each; dim_red: + the projection pcs' psi of every workgroup of a split (2 x nfull4 / 4 MFMAs per wave and tile)
   ctx->timers[10] = (double)plan.njobs * plan.nq * NWT * 128.0 + (b.k_pcs > 0 && !pre ? (double)plan.nsuper * nfull4 * 128.0 : 0.0);
+  // table entries per raw value that the in-loop build of this launch's kernel writes (0: a form without that build)
+  ctx->timers[16] = (pre || ext || plan.wpw == 8) ? 0.0 : a.pow3 ? 3.0 : 4.0;
   ctx->timers[15] = (double)plan.two_group_jobs;   // jobs of this launch's plan that span two A groups (0: a one-A-group plan)
   return KP_OK;
 }

@@ -34,6 +34,8 @@ struct Gram3Args {
   // has nsplit_fit = its split count and grp[0] = (alpha, beta, u)
   int nsplit_fit = 1 << 30;
   Gram3Src grp[KP_GRAM_GROUP_MAX] = {};
+  // launcher only: the in-kernel-lift monomial form of a dictionary without fourth powers runs its three-entry table (P3)
+  bool pow3 = false;
 };
 
 // one job per wave: kp_gram6_kernel<NQ, G4C> (kp_gram6.hip); hipErrorInvalidValue when no instantiation serves (nq, G4)
