@@ -79,7 +79,15 @@ int kp_device_info(const kp_ctx* ctx, char* name, int name_len, int* num_cu, int
  * kernel writes: 3 for a monomial dictionary without fourth powers and without a projection (its launches neither compute nor store
  * the x^4 entry that nothing reads), 4 otherwise; 0 for the forms that build no table in the loop (prelifted dim_red tiles, fourier /
  * gaussian entries, the eight-wave experiment).  The results do not depend on it, bit for bit; environment variable KP_GRAM3_POW3=0
- * (read once) keeps four entries everywhere for A/B runs and tests. */
+ * (read once) keeps four entries everywhere for A/B runs and tests.  17: not a time - which kernels the most recent rank-revealing
+ * solve ran (the fall-back of kp_fit_solve, kp_fit, kp_fit_refine and kp_model_project for a rank-deficient Gram matrix; 0 before the
+ * first one), as the decimal code 100 P + 10 S + R.  P, the panel kernel of the pivoted factorisation: 1 kp_pivchol_panel32_kernel<512>
+ * (W <= 512), 2 kp_pivchol_panel32_kernel<1024> (512 < W <= 560), 3 kp_pivchol_panel_kernel<512, 1> (W <= 512 under environment
+ * variable KP_PIVCHOL_GENERIC, read per call), 4 kp_pivchol_panel_kernel<1024, 1> (560 < W <= 1024, and 512 < W <= 560 under
+ * KP_PIVCHOL_GENERIC), 5 kp_pivchol_panel_kernel<1024, 4> (W > 1024).  S, the substitution of the LAST second stage at width n (the
+ * padded W, or the remembered rank rounded up to 16) with ncp padded right-hand sides: 1 kp_trsm2_kernel<1> (n <= 512, ncp <= 512), 2
+ * kp_trsm2_kernel<4> (n <= 512, ncp > 512), 3 the block substitution over all CUs (n > 512).  R: how many second stages ran - 2 when
+ * the remembered rank was too small and the substitution was repeated at full width.  The results do not depend on reading it. */
 int kp_timer_get(const kp_ctx* ctx, int which, double* ms);
 /* Device pointer + byte size of the library stream's raw handle, for profilers/benchmarks
  * that want to bracket work with their own HIP events: returns hipStream_t as void*. */

@@ -709,11 +709,14 @@ static int chol_solve_wide(kp_ctx* ctx, double* Gp, double* Cp, double* Dinv, in
 
 // For a caller that already holds a Cholesky factor (the rank-revealing solve, kp_pivchol.hip): Lp = n x n (n a multiple of
 // 16), L in the lower triangle; Cp (n x ncp, ncp a multiple of 16) := (L L')^-1 Cp.  Dinv: room for (n / 16) * 256 doubles.
-int kp_factor_substitute_dev(kp_ctx* ctx, double* Lp, int n, double* Cp, int ncp, double* Dinv, hipStream_t st) {
+// *form (or nullptr) receives which substitution ran: 1 kp_trsm2_kernel<1>, 2 kp_trsm2_kernel<4>, 3 wide_substitute (the S
+// digit of kp_timer_get(17)).
+int kp_factor_substitute_dev(kp_ctx* ctx, double* Lp, int n, double* Cp, int ncp, double* Dinv, hipStream_t st, int* form) {
   if (!st) st = ctx->stream;
   const int nbk = n / 16, npair = nbk * (nbk - 1) / 2;
   hipLaunchKernelGGL(kp_chol_finish_kernel, dim3(npair + nbk, 1), dim3(256), 0, st, Lp, n, npair, Dinv);
   KP_HIP(ctx, hipGetLastError());
+  if (form) *form = n > 16 * 4 * TR_MAXJ ? 3 : ncp <= 512 ? 1 : 2;
   if (n > 16 * 4 * TR_MAXJ) return wide_substitute(ctx, Lp, Cp, Dinv, n, ncp, st);
   static KpLdsCache trsm2_lds;
   KP_HIP(ctx, kp_ensure_lds(trsm2_lds, (const void*)kp_trsm2_kernel<4>, (size_t)352 * 16 * 8 > (size_t)n * 16 * 8 ? (size_t)352 * 16 * 8 : (size_t)n * 16 * 8));

@@ -91,7 +91,7 @@ struct kp_ctx {
   int64_t hbm_bytes = 0;
   std::string name;
   mutable std::string err;
-  double timers[17] = {0};            // (16: power-table entries per raw value written by the in-loop build of the last Kronecker Gram launch, 3 or 4; 15: jobs of the last Kronecker Gram launch's plan that span two A groups; kp_gram3.hip; 12: the group size of the Gram queue, 13: fits served by the launches of timer 7; kp_fit.hip; 14: kernel code of the most recent sweep call, not a time; kp_batch.hip)
+  double timers[18] = {0};            // (17: which panel kernel and substitution form the most recent rank-revealing solve ran, not a time; kp_pivchol.hip; 16: power-table entries per raw value written by the in-loop build of the last Kronecker Gram launch, 3 or 4; 15: jobs of the last Kronecker Gram launch's plan that span two A groups; kp_gram3.hip; 12: the group size of the Gram queue, 13: fits served by the launches of timer 7; kp_fit.hip; 14: kernel code of the most recent sweep call, not a time; kp_batch.hip)
   double gram_flops_per_pair = 0;
   // growable device workspaces
   void* ws[21] = {nullptr};     // slot 8: staging of the collectives, 9: rank-revealing solve, 10 / 11: Grams of the shadow dictionary of a dim_red fit, their half-transformed form
@@ -349,7 +349,7 @@ inline int kp_gram_dispatch(kp_ctx* ctx, const kp_basis* basis, const kp_snapsho
 bool kp_chol_ll_applicable(int n);
 hipError_t kp_chol_ll_launch(double* Gp, int n, int nb, int* info, int* sticky, int prof, hipStream_t st, const double* thr = nullptr);
 // substitution with a factor the caller already holds (kp_fit.hip)
-int kp_factor_substitute_dev(kp_ctx* ctx, double* Lp, int n, double* Cp, int ncp, double* Dinv, hipStream_t st);
+int kp_factor_substitute_dev(kp_ctx* ctx, double* Lp, int n, double* Cp, int ncp, double* Dinv, hipStream_t st, int* form = nullptr);
 int kp_copy_to_host_async(kp_ctx* ctx, const void* src_dev, void* dst_host, size_t bytes, int mapped, hipStream_t s);
 int kp_pivchol_solve_dev(kp_ctx* ctx, const double* G_dev, const double* C_dev, int W, int ncols, double* K_dev, int* rank, int rank_hint = 0,
                          void* k_host = nullptr, size_t k_bytes = 0, hipEvent_t ev_solved = nullptr, int k_host_mapped = 0);
