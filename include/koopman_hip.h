@@ -87,7 +87,14 @@ int kp_device_info(const kp_ctx* ctx, char* name, int name_len, int* num_cu, int
  * KP_PIVCHOL_GENERIC), 5 kp_pivchol_panel_kernel<1024, 4> (W > 1024).  S, the substitution of the LAST second stage at width n (the
  * padded W, or the remembered rank rounded up to 16) with ncp padded right-hand sides: 1 kp_trsm2_kernel<1> (n <= 512, ncp <= 512), 2
  * kp_trsm2_kernel<4> (n <= 512, ncp > 512), 3 the block substitution over all CUs (n > 512).  R: how many second stages ran - 2 when
- * the remembered rank was too small and the substitution was repeated at full width.  The results do not depend on reading it. */
+ * the remembered rank was too small and the substitution was repeated at full width.  The results do not depend on reading it.
+ * 18: not a time - the form of the most recent BATCHED solve of pipelined fits (two or more queued fits solved by one launch
+ * sequence; 0 before the first one), as the decimal code 100 E + 10 X + C.  E, the substitution's entry: 1 kp_trsm2_kernel<4>
+ * with registers for eight row blocks per wave, one workgroup per CU; 2 kp_trsm2_batch_kernel with six row blocks, two workgroups
+ * per CU, for padded widths up to 384.  X = 1: the workgroups of a system run on one die of the chip (csrc/kp_solve_xcd_map.h).  C = 1: the
+ * right-hand sides are read from the [G | C] ring and K is stored into its slot of the result ring by the substitution itself -
+ * no padded copy of C, no unpad launch.  211 or 100: the parts go together.  The results do not depend on it, bit for bit;
+ * environment variable KP_SOLVE_BATCH_FORM=0 (read once) keeps the launch sequence of code 100 everywhere for A/B runs and tests. */
 int kp_timer_get(const kp_ctx* ctx, int which, double* ms);
 /* Device pointer + byte size of the library stream's raw handle, for profilers/benchmarks
  * that want to bracket work with their own HIP events: returns hipStream_t as void*. */

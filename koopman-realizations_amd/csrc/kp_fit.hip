@@ -7,6 +7,10 @@
 //                      diagonal blocks
 //   kp_trsm_kernel     one wave per 16 right-hand sides: forward + backward substitution by
 //                      blocks with v_mfma_f64_16x16x4_f64, X block resident in LDS
+//   kp_trsm2_kernel    the substitution in use: right-looking, 4 waves, v_mfma_f64_4x4x4 (4 or 16 right-hand sides per workgroup)
+//   kp_trsm2_batch_kernel  the same body for the batched solve of pipelined fits (n <= 384): two workgroups per CU, a system's
+//                      workgroups on one die (kp_solve_xcd_map.h), C read from the [G | C] ring and K stored into the result
+//                      ring - no padded C, no unpad launch (KP_SOLVE_BATCH_FORM=0: the sequence of before; kp_timer_get(18))
 #include <cmath>
 #include <cstdlib>
 
@@ -15,6 +19,7 @@
 #include <cstring>
 
 #include "kp_internal.h"
+#include "kp_solve_xcd_map.h"
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 extern "C" int kp_synchronize(kp_ctx* ctx);
@@ -381,7 +386,10 @@ static bool trsm_old_sel() {
 // drained queue) per step - and uses v_mfma_f64_16x16x4, which runs at half the rate of the 4x4x4 form on gfx950 (140 against
 // 4 x 16.5 cycles per 2048 flop): a 16 x 16 x 16 tile product is 16 MFMAs here (blocks = the 4 row groups of the tile; the B
 // operand - a 4 x 4 block of Y_j - is shared by the blocks).
-#define TR2_MAXR 8   // row blocks per wave: ceil(32 / 4)  =>  n <= 512
+// MAXR = row blocks per wave the registers are sized for: 8 = ceil(32 / 4)  =>  n <= 512 (kp_trsm2_kernel); 6  =>  n <= 384, the
+// batched entry (kp_trsm2_batch_kernel), whose accumulators and tiles then leave room for two workgroups per CU
+#define TR2_MAXR 8
+#define TR2_BATCH_MAXR 6
 namespace {
 
 // LDS column order of a block of 4 NJ right-hand sides: a lane's NJ values (columns 4 J + jj) are contiguous
@@ -389,8 +397,8 @@ template <int NJ>
 __device__ __forceinline__ int tr2_col(int c) { return (c & 3) * NJ + (c >> 2); }
 
 // an[q][K] = -(A operand of tile (row(q), column block jc)): rows 4 blk + jj of the tile, column 4 K + kq
-template <int CNT>
-__device__ __forceinline__ void tr2_load(double (&an)[TR2_MAXR][4], const double* __restrict__ LU, int64_t n, int jc, const int (&rowof)[TR2_MAXR], int kq,
+template <int CNT, int MAXR>
+__device__ __forceinline__ void tr2_load(double (&an)[MAXR][4], const double* __restrict__ LU, int64_t n, int jc, const int (&rowof)[MAXR], int kq,
                                          int blk, int jj) {
 #pragma unroll
   for (int q = 0; q < CNT; ++q)
@@ -399,8 +407,8 @@ __device__ __forceinline__ void tr2_load(double (&an)[TR2_MAXR][4], const double
 }
 
 // slots [q0, CNT): R -= L Y  (4 NJ MFMAs per tile: NJ independent chains of 4)
-template <int CNT, int NJ>
-__device__ __forceinline__ void tr2_update(double (&acc)[TR2_MAXR][NJ], const double (&an)[TR2_MAXR][4], const double (&bv)[4][NJ], int q0) {
+template <int CNT, int NJ, int MAXR>
+__device__ __forceinline__ void tr2_update(double (&acc)[MAXR][NJ], const double (&an)[MAXR][4], const double (&bv)[4][NJ], int q0) {
 #pragma unroll
   for (int q = 0; q < CNT; ++q) {
     if (q < q0) continue;
@@ -451,6 +459,7 @@ __device__ __forceinline__ void tr2_read_b(const double* __restrict__ xs, int j,
 
 }  // namespace
 
+// (cases beyond the body's MAXR are discarded, not instantiated: CALL names MAXR)
 #define TR2_SWITCH(CALL)                                                                   \
   switch (cnt) {                                                                           \
     case 1: { constexpr int C_ = 1; CALL; } break;                                         \
@@ -459,8 +468,8 @@ __device__ __forceinline__ void tr2_read_b(const double* __restrict__ xs, int j,
     case 4: { constexpr int C_ = 4; CALL; } break;                                         \
     case 5: { constexpr int C_ = 5; CALL; } break;                                         \
     case 6: { constexpr int C_ = 6; CALL; } break;                                         \
-    case 7: { constexpr int C_ = 7; CALL; } break;                                         \
-    case 8: { constexpr int C_ = 8; CALL; } break;                                         \
+    case 7: if constexpr (MAXR >= 7) { constexpr int C_ = 7; CALL; } break;                \
+    case 8: if constexpr (MAXR >= 8) { constexpr int C_ = 8; CALL; } break;                \
     default: break;                                                                        \
   }
 
@@ -471,25 +480,32 @@ __device__ __forceinline__ void tr2_read_b(const double* __restrict__ xs, int j,
 // ldl / ldx: leading dimensions of LU and X (the blocked factorisation of wide systems, kp_wide.hip, substitutes against a
 // diagonal block that sits inside a larger matrix and right-hand sides that are rows of one); dirs: 1 = forward only,
 // 2 = backward only, 3 = both.
-template <int NJ>
-__global__ __launch_bounds__(256) void kp_trsm2_kernel(const double* __restrict__ LU, const double* __restrict__ Dinv, int n, int ncp,
-                                                      double* __restrict__ X, double* __restrict__ Kout, int W, int ncols, int64_t ldl, int64_t ldx,
-                                                      int dirs, const int* __restrict__ info) {
-  // (info: the factorisation's status word(s), or nullptr - a factor that hit a non-positive pivot is not substituted with:
-  // the caller reads the same word and takes the rank-revealing path)
-  if (info && info[blockIdx.y]) return;
+// The body, for column block cb of ONE system (LU, Dinv, X already point at it).  MAXR: above.  RING: the right-hand sides are read
+// where the caller keeps them (Cin: W x ncols, leading dimension W; zeros for the padding rows and columns) and not from X, which
+// is not touched, and the solution goes to Kout: the batched entry, which needs neither a padded copy of C in front of it nor an
+// unpad launch behind it.
+template <int NJ, int MAXR, bool RING>
+__device__ __forceinline__ void tr2_body(const double* __restrict__ LU, const double* __restrict__ Dinv, int n, double* __restrict__ X,
+                                         const double* __restrict__ Cin, double* __restrict__ Kout, int W, int ncols, int64_t ldl, int64_t ldx, int dirs,
+                                         int cb) {
   extern __shared__ __align__(16) double xs[];  // [n][4 NJ] X block, columns in tr2_col order
   constexpr int NC = 4 * NJ;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int cb = blockIdx.x;
   const int nt = n / 16;
   const int kq = lane >> 4, blk = (lane >> 2) & 3, jj = lane & 3;
-  LU += blockIdx.y * (size_t)n * n; Dinv += blockIdx.y * (size_t)nt * 256; X += blockIdx.y * (size_t)ldx * ncp;   // system of a batch
-  double* Xb = X + (size_t)cb * NC * ldx;
+  double* Xb = nullptr;                                   // (RING: there is no X)
+  if constexpr (!RING) Xb = X + (size_t)cb * NC * ldx;
   for (int e = tid; e < n * NC; e += 256) {
     int row = e % n, col = e / n;
-    xs[row * NC + tr2_col<NJ>(col)] = Xb[(size_t)col * ldx + row];       // C block -> LDS (overwritten by Y, then K)
+    double v;
+    if constexpr (RING) {
+      const int gc = cb * NC + col;
+      v = (row < W && gc < ncols) ? Cin[(size_t)gc * W + row] : 0.0;
+    } else {
+      v = Xb[(size_t)col * ldx + row];
+    }
+    xs[row * NC + tr2_col<NJ>(col)] = v;                                 // C block -> LDS (overwritten by Y, then K)
   }
   __syncthreads();
   const int nown = wave < nt ? (nt - wave + 3) / 4 : 0;    // row blocks wave, wave + 4, ... < nt
@@ -498,12 +514,12 @@ __global__ __launch_bounds__(256) void kp_trsm2_kernel(const double* __restrict_
     // slot q <-> row block, the rows that retire LAST first, so that the rows a step still reaches are always the slots
     // [0, cnt) and the row that retires next is slot cnt - 1: forward rows retire ascending (slot 0 = the largest row),
     // backward descending (slot 0 = the smallest)
-    int rowof[TR2_MAXR];
+    int rowof[MAXR];
 #pragma unroll
-    for (int q = 0; q < TR2_MAXR; ++q) rowof[q] = q < nown ? (dir == 0 ? wave + 4 * (nown - 1 - q) : wave + 4 * q) : 0;
-    double acc[TR2_MAXR][NJ];                              // R(4 blk + kq, 4 J + jj) of the slot's row block
+    for (int q = 0; q < MAXR; ++q) rowof[q] = q < nown ? (dir == 0 ? wave + 4 * (nown - 1 - q) : wave + 4 * q) : 0;
+    double acc[MAXR][NJ];                              // R(4 blk + kq, 4 J + jj) of the slot's row block
 #pragma unroll
-    for (int q = 0; q < TR2_MAXR; ++q) tr2_get<NJ>(xs, rowof[q] * 16 + 4 * blk + kq, jj, acc[q]);
+    for (int q = 0; q < MAXR; ++q) tr2_get<NJ>(xs, rowof[q] * 16 + 4 * blk + kq, jj, acc[q]);
     // owned rows strictly beyond row j in sweep direction (= the rows the update with X_j reaches)
     auto beyond = [&](int j) {
       const int c = dir == 0 ? nown - (j < wave ? 0 : (j - wave) / 4 + 1) : (j <= wave ? 0 : (j - wave + 3) / 4);
@@ -526,7 +542,7 @@ __global__ __launch_bounds__(256) void kp_trsm2_kernel(const double* __restrict_
       while (jf >= 0 && jf < nt && (jf & 3) != wave) jf += jstep;
       load_dinv(jf, dv);
     }
-    double an[TR2_MAXR][4];
+    double an[MAXR][4];
     double bv[4][NJ];
     int cnt = nown;                                        // rows reached by "X_{j0 - jstep}": all of them (nothing pending)
     for (int it = 0; it < nt; ++it) {
@@ -535,12 +551,12 @@ __global__ __launch_bounds__(256) void kp_trsm2_kernel(const double* __restrict_
       // here: an / bv = tiles of column j - jstep for the slots [0, cnt) and X_{j - jstep} (it > 0), not yet applied
       if (owner) {
         const int qj = cnt - 1;                            // slot of row j
-        if (it > 0) { TR2_SWITCH((tr2_update<C_, NJ>(acc, an, bv, C_ - 1))); }      // row j alone
+        if (it > 0) { TR2_SWITCH((tr2_update<C_, NJ, MAXR>(acc, an, bv, C_ - 1))); }      // row j alone
         double rj[NJ];
 #pragma unroll
         for (int J = 0; J < NJ; ++J) rj[J] = acc[0][J];
 #pragma unroll
-        for (int q = 1; q < TR2_MAXR; ++q)
+        for (int q = 1; q < MAXR; ++q)
           if (q == qj) {
 #pragma unroll
             for (int J = 0; J < NJ; ++J) rj[J] = acc[q][J];
@@ -564,13 +580,13 @@ __global__ __launch_bounds__(256) void kp_trsm2_kernel(const double* __restrict_
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         tr2_put<NJ>(xs, j * 16 + 4 * blk + kq, jj, y);
         load_dinv(j + 4 * jstep, dv);
-        if (it > 0) { TR2_SWITCH((tr2_update<C_ - 1, NJ>(acc, an, bv, 0))); }      // the rest of this wave's rows
+        if (it > 0) { TR2_SWITCH((tr2_update<C_ - 1, NJ, MAXR>(acc, an, bv, 0))); }      // the rest of this wave's rows
       } else if (it > 0) {
-        TR2_SWITCH((tr2_update<C_, NJ>(acc, an, bv, 0)));
+        TR2_SWITCH((tr2_update<C_, NJ, MAXR>(acc, an, bv, 0)));
       }
       // tiles of column j for the rows beyond it: requested now, used after the barrier
       cnt = beyond(j);
-      TR2_SWITCH((tr2_load<C_>(an, LU, ldl, j, rowof, kq, blk, jj)));
+      TR2_SWITCH((tr2_load<C_, MAXR>(an, LU, ldl, j, rowof, kq, blk, jj)));
       // LDS-only barrier: the tile loads just issued stay in flight across it (a __syncthreads would wait for them)
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
       tr2_read_b<NJ>(xs, j, kq, jj, bv);
@@ -580,13 +596,51 @@ __global__ __launch_bounds__(256) void kp_trsm2_kernel(const double* __restrict_
   for (int e = tid; e < n * NC; e += 256) {
     int row = e % n, col = e / n;
     const double v = xs[row * NC + tr2_col<NJ>(col)];
-    if (Kout) {
+    if (RING || Kout) {
       const int gc = cb * NC + col;
       if (row < W && gc < ncols) Kout[(size_t)gc * W + row] = v;
     } else {
       Xb[(size_t)col * ldx + row] = v;
     }
   }
+}
+
+template <int NJ>
+__global__ __launch_bounds__(256) void kp_trsm2_kernel(const double* __restrict__ LU, const double* __restrict__ Dinv, int n, int ncp,
+                                                      double* __restrict__ X, double* __restrict__ Kout, int W, int ncols, int64_t ldl, int64_t ldx,
+                                                      int dirs, const int* __restrict__ info) {
+  // (info: the factorisation's status word(s), or nullptr - a factor that hit a non-positive pivot is not substituted with:
+  // the caller reads the same word and takes the rank-revealing path)
+  if (info && info[blockIdx.y]) return;
+  const int nt = n / 16;
+  LU += blockIdx.y * (size_t)n * n; Dinv += blockIdx.y * (size_t)nt * 256; X += blockIdx.y * (size_t)ldx * ncp;   // system of a batch
+  tr2_body<NJ, TR2_MAXR, false>(LU, Dinv, n, X, (const double*)nullptr, Kout, W, ncols, ldl, ldx, dirs, (int)blockIdx.x);
+}
+
+// The batched entry of the pipelined fits (kp_chol_solve_batch_dev, nb > 1, n <= 16 * 4 * TR2_BATCH_MAXR = 384): 16 right-hand
+// sides per workgroup as kp_trsm2_kernel<4>, the same MFMA chains in the same order - K is the same bits - and
+//   * registers for six row blocks per wave and two workgroups per CU: the kernel waits for L tiles and barriers most of its
+//     time, so a second resident workgroup fills the first one's waits;
+//   * a flat grid in kp_solve_xcd_map order: the column blocks of a system run on ONE die and share its L2's copy of L;
+//   * C read from the [G | C] ring (system stride gc_stride) and K stored into its slot of the result ring,
+//     K + ((k_first + system) % k_cap) W ncols (k_cap = 0: K): no padded copy of C, no unpad launch.
+// A system whose factorisation failed (info[system] set) leaves its C in its K slot, as pad + unpad did.
+__global__ __launch_bounds__(256, 2) void kp_trsm2_batch_kernel(const double* __restrict__ LU, const double* __restrict__ Dinv, int n, int ncp, int nb,
+                                                                const double* __restrict__ C, size_t gc_stride, double* __restrict__ K, int W,
+                                                                int ncols, int k_first, int k_cap, const int* __restrict__ info) {
+  int sys, cb;
+  if (!kp_solve_xcd_map(blockIdx.x, ncp / 16, nb, &sys, &cb)) return;
+  C += sys * gc_stride;
+  if (k_cap > 0) K += (size_t)((k_first + sys) % k_cap) * W * ncols;
+  if (info[sys]) {
+    for (int e = threadIdx.x; e < W * 16; e += 256) {
+      const int row = e % W, gc = cb * 16 + e / W;
+      if (gc < ncols) K[(size_t)gc * W + row] = C[(size_t)gc * W + row];
+    }
+    return;
+  }
+  const int nt = n / 16;
+  tr2_body<4, TR2_BATCH_MAXR, true>(LU + sys * (size_t)n * n, Dinv + sys * (size_t)nt * 256, n, (double*)nullptr, C, K, W, ncols, (int64_t)n, (int64_t)n, 3, cb);
 }
 
 // ---- systems beyond one workgroup's reach (n > 512): blocked right-looking factorisation over MANY workgroups ------------------
@@ -728,8 +782,18 @@ int kp_factor_substitute_dev(kp_ctx* ctx, double* Lp, int n, double* Cp, int ncp
   return KP_OK;
 }
 
+// KP_SOLVE_BATCH_FORM (read once): unset or 1 - a batch (nb > 1) of systems up to n = 384 is substituted by
+// kp_trsm2_batch_kernel, C padded by nobody and K unpadded by nobody; 0 - the launch sequence of before (pad G and C,
+// kp_trsm2_kernel<4> on a (column block, system) grid, unpad), for A/B runs and tests/test_gpu_solve_batch_forms.py.
+static bool solve_batch_form_new() {
+  static const bool v = [] { const char* e = getenv("KP_SOLVE_BATCH_FORM"); return !e || atoi(e) != 0; }();
+  return v;
+}
+
 // nb systems [G | C] gc_stride doubles apart (W x W each; ncols = W when nb > 1); system y's K goes to
 // K_dev + ((k_first + y) % k_cap) W ncols (k_cap = 0: K_dev).  One launch sequence for the whole batch.
+// kp_timer_get(18) afterwards, for nb > 1: 100 E + 10 X + C - E the substitution's entry (1 kp_trsm2_kernel<4>, 2
+// kp_trsm2_batch_kernel), X = 1: workgroups in kp_solve_xcd_map order, C = 1: no copies of C and K around it.
 int kp_chol_solve_batch_dev(kp_ctx* ctx, const double* G_dev, const double* C_dev, int W, int ncols, int nb, size_t gc_stride, double* K_dev,
                             int k_first, int k_cap, hipStream_t st, hipEvent_t pad_done, int* sticky) {
   if (!st) st = ctx->stream;
@@ -746,7 +810,10 @@ int kp_chol_solve_batch_dev(kp_ctx* ctx, const double* G_dev, const double* C_de
   const bool wide = n > 16 * 4 * TR_MAXJ;
   if (wide && nb != 1) return ctx->fail(KP_ERR_ARG, "kp_fit_solve: systems wider than 512 are solved one at a time");
   if (!wide && (lds_chol > 160 * 1024 - 8192 || lds_trsm > 160 * 1024)) return ctx->fail(KP_ERR_ARG, "kp_fit_solve: W too large");
-  hipLaunchKernelGGL(kp_pad_kernel, dim3((n + 255) / 256, n + ncp, nb), dim3(256), 0, st, G_dev, C_dev, W, ncols, n, ncp, Gp, Cp, gc_stride);
+  // the batched entry reads C from the ring and writes K into its slot: only G is padded (the grid's first n columns)
+  const bool batch_entry = nb > 1 && !wide && n <= 16 * 4 * TR2_BATCH_MAXR && solve_batch_form_new() && !trsm_old_sel();
+  if (nb > 1) ctx->timers[18] = batch_entry ? 211.0 : 100.0;
+  hipLaunchKernelGGL(kp_pad_kernel, dim3((n + 255) / 256, batch_entry ? n : n + ncp, nb), dim3(256), 0, st, G_dev, C_dev, W, ncols, n, ncp, Gp, Cp, gc_stride);
   KP_HIP(ctx, hipGetLastError());
   if (pad_done) KP_HIP(ctx, hipEventRecord(pad_done, st));
   if (wide) {      // blocked factorisation and substitution over all CUs
@@ -782,7 +849,14 @@ int kp_chol_solve_batch_dev(kp_ctx* ctx, const double* G_dev, const double* C_de
                        (int64_t)n, 3, (const int*)info);
     KP_HIP(ctx, hipGetLastError());
     return KP_OK;
-  } else {                    // a batch: 16 per workgroup, every workgroup reads all of L
+  } else if (batch_entry) {   // a batch up to n = 384: two workgroups per CU, a system per die, C and K where they lie
+    static KpLdsCache batch_lds;
+    KP_HIP(ctx, kp_ensure_lds(batch_lds, (const void*)kp_trsm2_batch_kernel, (size_t)n * 16 * 8));
+    hipLaunchKernelGGL(kp_trsm2_batch_kernel, dim3(kp_solve_xcd_grid(ncp / 16, nb)), dim3(256), (size_t)n * 16 * 8, st, Gp, Dinv, n, ncp, nb, C_dev, gc_stride,
+                       K_dev, W, ncols, k_first, k_cap, (const int*)info);
+    KP_HIP(ctx, hipGetLastError());
+    return KP_OK;
+  } else {                    // a wider batch (or KP_SOLVE_BATCH_FORM=0): 16 per workgroup, every workgroup reads all of L
     static KpLdsCache trsm2_lds;
     KP_HIP(ctx, kp_ensure_lds(trsm2_lds, (const void*)kp_trsm2_kernel<4>, (size_t)n * 16 * 8));
     hipLaunchKernelGGL((kp_trsm2_kernel<4>), dim3(ncp / 16, nb), dim3(256), (size_t)n * 16 * 8, st, Gp, Dinv, n, ncp, Cp, (double*)nullptr, W, ncols,
