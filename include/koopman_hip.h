@@ -237,8 +237,9 @@ int kp_fit_get_K(kp_ctx* ctx, int index, int W, double* K);
  * (3 Ns W doubles of device memory): the accuracy path, not the throughput path. */
 int kp_fit_refine(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* snaps, int steps, double* K);
 /* kp_fit with K_out == NULL and one least-squares value is ASYNCHRONOUS: it returns when the work is
- * enqueued; the solve runs on a second HIP stream so that it overlaps the fused Gram kernel of the
- * next kp_fit call (sweeps over many fits, train_models loop Ksysid.m:1372-1387 / evaluate_rand_models.m:45-144).
+ * enqueued; its solve is DEFERRED: the [G | C] pairs of the queued fits wait in a device ring and are factored and
+ * solved by one batched launch sequence on the same HIP stream, so that nothing runs beside a fused Gram kernel
+ * (sweeps over many fits, train_models loop Ksysid.m:1372-1387 / evaluate_rand_models.m:45-144).
  * kp_synchronize waits for everything in flight and returns KP_ERR_NOT_SPD if a deferred fit failed; kp_fit_get_K,
  * kp_fit_gram, kp_fit_solve and kp_destroy synchronise implicitly.
  * The fits issued since the previous kp_synchronize form a BATCH; fit number q of the batch keeps its K in slot

@@ -57,9 +57,6 @@ extern "C" int kp_create(int device_id, kp_ctx** out) {
   for (int i = 0; i < 64; ++i) (void)hipEventCreateWithFlags(&c->ring_red[i], evf);
   (void)hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking);
   (void)hipEventCreateWithFlags(&c->ev_gram_done, hipEventDisableTiming | evf);
-  (void)hipEventCreateWithFlags(&c->ev_pad_done, hipEventDisableTiming | evf);
-  (void)hipEventCreateWithFlags(&c->ev_pad_done2, hipEventDisableTiming | evf);
-  (void)hipEventCreateWithFlags(&c->ev_main_done, hipEventDisableTiming | evf);
   (void)hipEventCreateWithFlags(&c->ev_solve0, evf);
   (void)hipEventCreateWithFlags(&c->ev_solve1, evf);
   if (hipMalloc((void**)&c->sticky_info, sizeof(int)) == hipSuccess) (void)hipMemset(c->sticky_info, 0, sizeof(int));
@@ -89,9 +86,6 @@ extern "C" int kp_destroy(kp_ctx* c) {
   if (c->pin_small) (void)hipHostFree(c->pin_small);
   if (c->pin_scratch) (void)hipHostFree(c->pin_scratch);
   if (c->ev_gram_done) (void)hipEventDestroy(c->ev_gram_done);
-  if (c->ev_pad_done) (void)hipEventDestroy(c->ev_pad_done);
-  if (c->ev_pad_done2) (void)hipEventDestroy(c->ev_pad_done2);
-  if (c->ev_main_done) (void)hipEventDestroy(c->ev_main_done);
   if (c->ev_solve0) (void)hipEventDestroy(c->ev_solve0);
   if (c->ev_solve1) (void)hipEventDestroy(c->ev_solve1);
   if (c->stream2) (void)hipStreamDestroy(c->stream2);

@@ -1032,7 +1032,7 @@ static int64_t gram3_slots(const kp_ctx* ctx, const kp_gram3_plan& plan, int* nc
   if (const char* ov = getenv("KP_GRAM3_WGPCU")) wg_per_cu = std::max(1, atoi(ov));
   if (ncu_out) *ncu_out = ncu;
   if (wgpcu_out) *wgpcu_out = wg_per_cu;
-  return (int64_t)std::max(8, ncu - ctx->reserve_cus) * wg_per_cu;
+  return (int64_t)std::max(8, ncu) * wg_per_cu;
 }
 
 // Fits that may share a Gram launch (kp_fit.hip's queue of pipelined fits): the in-kernel-lift monomial form of kp_gram3_kernel -
@@ -1084,10 +1084,8 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   if (kps < 1) kps = 1;
   nsplit = (int)std::max<int64_t>(1, (ktiles + kps - 1) / kps);
   size_t per_split = (size_t)plan.njobs * plan.nq * NWT * 64;
-  // asynchronous fits: two partial buffers, so that the next Gram kernel may run while the solve stream reduces this one
-  const size_t part_bytes = ((size_t)n * nsplit * per_split * 8 + 255) & ~(size_t)255;
-  // sized for the largest split count of this dictionary at once: a workspace that grows with the snapshot count would put
-  // a hipFree + hipMalloc of ~80 MB (17 ms, and a device synchronisation) into the first large fit of a running pipeline
+  // the split partials (workspace 4), sized for the largest split count of this dictionary at once: a workspace that grows
+  // with the snapshot count would put a hipFree + hipMalloc of ~80 MB (17 ms, and a device synchronisation) into the first large fit of a running pipeline
   // (... and for both plans of the dictionary, the cover plan built now if it has one: synchronous and pipelined fits of it
   // may alternate, whichever comes first)
   if (gram3_cover_mode() != 0) {
@@ -1099,9 +1097,8 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   for (const kp_gram3_plan* o : {(const kp_gram3_plan*)basis->plan3, (const kp_gram3_plan*)basis->plan3->cover})
     if (o && o != &plan)
       part_max = std::max(part_max, ((size_t)((int64_t)ncu * wg_per_cu / o->nsuper) * o->njobs * o->nq * NWT * 64 * 8 + 255) & ~(size_t)255);
-  char* part_base = (char*)ctx->workspace(4, part_max * (ctx->reduce_stream ? 2 : 1));
-  if (!part_base) return ctx->fail(KP_ERR_HIP, "kp_fit_gram: out of device memory");
-  double* part = (double*)(part_base + (ctx->reduce_stream ? (size_t)ctx->part_flip * part_bytes : 0));
+  double* part = (double*)ctx->workspace(4, part_max);
+  if (!part) return ctx->fail(KP_ERR_HIP, "kp_fit_gram: out of device memory");
 
   // dim_red dictionaries: the econ lift once per snapshot into a row buffer (kp_gram3_prelift.hip), the Gram kernel loads tiles of it.
   // Round 4's prelift kernel walked its 84 columns in ~40 us however few threads ran, so the in-kernel projection won below
@@ -1160,9 +1157,8 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   a.pow3 = !pre && b.k_pcs == 0 && !ext && plan.wpw == 4 && basis->pow_depth <= 3 && (BM < 2 || gram3_tup(BM)) && gram3_pow3_on();
   const int grid = plan.nsuper * nsplit * n;
   // every event record is a barrier packet the command processor works through between two Gram kernels: the
-  // pipelined path keeps two (kernel start / end; the end also releases the reduction on the solve stream)
-  const bool pipelined = ctx->reduce_stream || ctx->ring_timing;
-  if (!pipelined) KP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  // pipelined path (ring_timing) keeps two (kernel start / end)
+  if (!ctx->ring_timing) KP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   hipEvent_t ev_start = ctx->evp[0], ev_end = ctx->evp[1];
   // deferred-solve pipeline: every event record is a barrier packet between two Gram kernels, so only every 4th launch
   // is timed (the mean over the ring is what kp_synchronize reports)
@@ -1171,12 +1167,12 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   // keeps the every-4th rule and records no third event.
   const bool timed = !ctx->ring_timing || (ctx->ring_group && n > 1) || (ctx->ring_skip++ & 3) == 0;
   hipEvent_t ev_red = nullptr;
-  if (pipelined && timed) {                       // pipelined fits: a ring of event pairs, averaged at kp_synchronize
+  if (ctx->ring_timing && timed) {                // pipelined fits: a ring of event pairs, averaged at kp_synchronize
     ev_start = ctx->ring[2 * ctx->ring_pos];
     ev_end = ctx->ring[2 * ctx->ring_pos + 1];
     ctx->ring_members[ctx->ring_pos] = n;
     ctx->ring_has_red[ctx->ring_pos] = false;
-    if (ctx->ring_timing && ctx->ring_group && n > 1) {   // (a group of one records what a single launch recorded before: nothing behind its reduction)
+    if (ctx->ring_group && n > 1) {   // (a group of one records what a single launch recorded before: nothing behind its reduction)
       ev_red = ctx->ring_red[ctx->ring_pos];
       ctx->ring_has_red[ctx->ring_pos] = ev_red != nullptr;
     }
@@ -1202,20 +1198,14 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   }
   KP_HIP(ctx, e);
   if (timed) KP_HIP(ctx, hipEventRecord(ev_end, ctx->stream));
-  hipStream_t rs = ctx->stream;
-  if (ctx->reduce_stream) {                       // reduction (and everything after it) belongs to the solve stream
-    rs = ctx->reduce_stream;
-    KP_HIP(ctx, hipStreamWaitEvent(rs, ev_end, 0));
-    KP_HIP(ctx, hipEventRecord(ctx->evp[4], rs));   // start of the reduction on its own stream (timer 6)
-    ctx->solve_chained = true;                      // the solve stream already waits for this Gram kernel
-  }
-  ctx->reduce_timed_from = ctx->reduce_stream ? 4 : 1;
-  hipLaunchKernelGGL(kp_gram3_reduce_kernel, dim3(plan.njobs * plan.nq * NWT, n), dim3(nsplit >= 128 ? 1024 : nsplit >= 32 ? 512 : 256), 0, rs, part, nsplit, plan.njobs,
+  hipLaunchKernelGGL(kp_gram3_reduce_kernel, dim3(plan.njobs * plan.nq * NWT, n), dim3(nsplit >= 128 ? 1024 : nsplit >= 32 ? 512 : 256), 0, ctx->stream, part, nsplit, plan.njobs,
                      plan.nq, NWT, BM, plan.desc, plan.G4, N, W, GC_dev, GC_dev + (size_t)W * W, plan.wpw != 8 && gram3_tup(BM) ? 1 : 0, plan.dst_off, plan.dst);
   KP_HIP(ctx, hipGetLastError());
-  if (ev_red) KP_HIP(ctx, hipEventRecord(ev_red, rs));
-  if (!pipelined) KP_HIP(ctx, hipEventRecord(ctx->ev1, rs));
-  if (!ctx->ring_timing) KP_HIP(ctx, hipEventRecord(ctx->evp[2], rs));
+  if (ev_red) KP_HIP(ctx, hipEventRecord(ev_red, ctx->stream));
+  if (!ctx->ring_timing) {
+    KP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    KP_HIP(ctx, hipEventRecord(ctx->evp[2], ctx->stream));
+  }
   ctx->gram_flops_per_pair = (double)W * (W + 1) + 2.0 * W * W;
   // executed on the matrix pipe per pair (timer 10), of the plan THIS launch ran: jobs (padding included) x quads x weights MFMAs per 4 snapshots, 512 flop
   // each; dim_red: + the projection pcs' psi of every workgroup of a split (2 x nfull4 / 4 MFMAs per wave and tile)
@@ -1291,11 +1281,9 @@ int kp_gram3_linear_launch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshot
   const int N = basis->dev.N, m = basis->dev.m, W = basis->dev.W, Wb = sh->dev.W;
   double* tmp = (double*)ctx->workspace(10, (size_t)2 * Wb * Wb * 8);
   if (!tmp) return ctx->fail(KP_ERR_HIP, "kp_fit_gram: out of device memory");
-  // the reduction (and with it the gather) may belong to the solve stream of the asynchronous pipeline
-  hipStream_t rs = ctx->reduce_stream ? ctx->reduce_stream : ctx->stream;
   int rc = kp_gram3_launch(ctx, sh, s, tmp);
   if (rc) return rc;
-  hipLaunchKernelGGL(kp_gram3_linear_gather_kernel, dim3((2 * W * W + 255) / 256), dim3(256), 0, rs, tmp, N, m, Wb, GC_dev);
+  hipLaunchKernelGGL(kp_gram3_linear_gather_kernel, dim3((2 * W * W + 255) / 256), dim3(256), 0, ctx->stream, tmp, N, m, Wb, GC_dev);
   KP_HIP(ctx, hipGetLastError());
   ctx->gram_flops_per_pair = (double)W * (W + 1) + 2.0 * W * W;
   // timer 10 (flop EXECUTED on the matrix pipe per pair) stays what the inner launch set: the work added here - the gather, the

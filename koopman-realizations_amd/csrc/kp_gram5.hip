@@ -408,7 +408,7 @@ int kp_gram5_launch(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapshots* s,
   const size_t lds = (size_t)LDS5_DOUBLES * sizeof(double);
   int64_t ktiles = (s->Ns + KT5 - 1) / KT5;
   int ncu = ctx->num_cu > 0 ? ctx->num_cu : 256;
-  int64_t slots = (int64_t)std::max(8, ncu - ctx->reserve_cus) * 2;      // two workgroups share a CU
+  int64_t slots = (int64_t)std::max(8, ncu) * 2;     // two workgroups share a CU
   int nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(ktiles, slots / plan.nsuper > 0 ? slots / plan.nsuper : 1));
   int kps = (int)((ktiles + nsplit - 1) / nsplit);
   if (kps < 1) kps = 1;

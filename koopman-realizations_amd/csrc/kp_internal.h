@@ -33,44 +33,44 @@ struct kp_ctx {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t evp[6] = {nullptr};   // gram start, gram end, reduce end, solve end, spare x2
-  // asynchronous fit pipeline (kp_fit with K_out == NULL): Gram on `stream`, solve on `stream2`
+  // second stream of the synchronous fit: the plain solve beside the rank-revealing one of a dictionary with a rank hint
   hipStream_t stream2 = nullptr;
-  hipEvent_t ev_gram_done = nullptr, ev_pad_done = nullptr, ev_pad_done2 = nullptr, ev_solve0 = nullptr, ev_solve1 = nullptr;
-  bool pad_pending = false, pad_pending2 = false, async_pending = false;
-  int gc_flip = 0;             // asynchronous fits alternate between the two halves of GC
-  // results of asynchronous fits: ring of kring_cap slots in Kres; fit number q of the current batch (the fits since
-  // the last kp_synchronize) lives in slot q % kring_cap
-  int kring_cap = 128;   // = the default solve batch (solve_batch_size): a full 128-fit batch needs no kp_fit_async_slots call
-  int async_count = 0;         // asynchronous fits issued in the current batch
-  bool batch_closed = true;    // kp_synchronize closed the batch: the next asynchronous fit starts a new one
-  bool kres_is_ring = false;   // Kres currently holds an asynchronous batch (kp_fit_get_K indexes the ring)
+  hipEvent_t ev_gram_done = nullptr;
+  // ---- pipelined fits (kp_fit with K_out == NULL; kp_fit.hip): everything runs on `stream` ----
+  // A fit takes the next free slot of the [G | C] ring (GC) and, as fit number q of the current batch (the fits since the last
+  // kp_synchronize), slot q % kring_cap of the result ring (Kres).  Invariants:
+  //   * slots are consecutive: the pend_solves fits awaiting their solve hold [G | C] slots 0 .. pend_solves - 1 and result
+  //     slots pend_first .. pend_first + pend_solves - 1 (mod kring_cap); the pend_ngrams newest of them also await their Gram
+  //     launch, their [G | C] slots starting at pend_gram_gc
+  //   * pend_first is set (to async_count) when pend_solves == 0, i.e. by the first fit of every solve batch
+  //   * a failed group launch takes its members back: pend_solves and async_count drop by the group's size, so that no solve
+  //     factors an unwritten [G | C] slot and no kp_fit_get_K serves one
+  // Everything that enqueues on `stream`, reads a result or frees what a queued fit points to launches the Gram queue first
+  // (kp_flush_grams); kp_synchronize launches the solves (kp_flush_pending) and waits.
+  bool async_pending = false;  // fits were enqueued since the last kp_synchronize
+  int kring_cap = 128;         // result slots; = the default solve batch: a full 128-fit batch needs no kp_fit_async_slots call
+  int async_count = 0;         // fits issued in the current batch
+  bool batch_closed = true;    // kp_synchronize closed the batch: the next pipelined fit starts a new one
+  bool kres_is_ring = false;   // Kres currently holds a pipelined batch (kp_fit_get_K indexes the ring)
   const void* pend_basis = nullptr;   // dictionary / snapshot count / width of the fits in flight: a change drains the pipeline
   int64_t pend_Ns = 0;
   int pend_W = 0;
-  // deferred solves of the asynchronous pipeline: the Gram pairs of up to solve_batch fits wait in the [G | C] ring and are
-  // factored / solved by ONE batched launch sequence (no CUs held back for a concurrent solve stream)
+  // solve queue: the Gram pairs of up to KP_SOLVE_BATCH fits wait in the [G | C] ring and are factored / solved by ONE
+  // batched launch sequence (kp_chol_solve_batch_dev)
   int pend_solves = 0, pend_first = 0;
-  bool ring_timing = false;           // Gram launchers time themselves with the event ring and record nothing else
-  unsigned ring_skip = 0;
-  // Gram queue of the deferred-solve pipeline (kp_fit.hip): up to KP_GRAM_GROUP fits of one dictionary and snapshot count wait
-  // here and run as ONE Gram launch and ONE partial reduction (kp_gram3_launch_group); their [G | C] slots in the ring are
-  // consecutive, pend_gram_gc the first.  Everything that enqueues on `stream`, reads a result or frees what a queued fit
-  // points to launches the queue first (kp_flush_grams).
+  hipEvent_t ev_solve0 = nullptr, ev_solve1 = nullptr;   // around the most recent batched solve (timer 1)
+  int* sticky_info = nullptr;         // device word: set by any deferred factorisation that hit a non-positive pivot
+  // Gram queue: up to KP_GRAM_GROUP fits of one dictionary and snapshot count wait here and run as ONE Gram launch and ONE
+  // partial reduction (kp_gram3_launch_group)
   const kp_snapshots* pend_grams[KP_GRAM_GROUP_MAX] = {};
   int pend_ngrams = 0;
   const kp_basis* pend_gram_basis = nullptr;
   double* pend_gram_gc = nullptr;
-  bool ring_group = false;            // set around a launch of the Gram queue: the launch and its reduction are timed per group
-  kp_comm_state* comm = nullptr;      // set by kp_comm_create: rank / world / RCCL communicator
-  std::atomic<bool> comm_abandoned{false};   // kp_comm_abandon: a bootstrap still blocked in another thread must not publish `comm`
-  bool gc_preloaded = false;          // kp_multi_fit_sharded: ctx->GC already holds the summed [G | C] of all devices - kp_fit skips its Gram launch
-  bool reduce_grams = false;          // kp_fit_sharded: all-reduce [G | C] over the ranks between the Gram kernel and the solve
-  // set by the asynchronous kp_fit around kp_gram_dispatch: the split-partial reduction runs on this stream
-  // (after an event recorded behind the main Gram kernel) and the partial buffer `part_flip` is used
-  hipStream_t reduce_stream = nullptr;
-  hipEvent_t ev_main_done = nullptr;
-  // start / end events of the most recent pipelined Gram launches (ring of KP_RING pairs): kp_synchronize reports the
+  // timers: start / end events of the most recent pipelined Gram launches (a ring of 64 pairs): kp_synchronize reports the
   // MEAN kernel duration over them (timer 0), not just the last launch
+  bool ring_timing = false;           // set around a pipelined Gram launch: it times itself with the event ring and records nothing else
+  bool ring_group = false;            // set around a launch of the Gram queue: the launch and its reduction are timed per group
+  unsigned ring_skip = 0;
   hipEvent_t ring[2 * 64] = {};
   int ring_pos = 0, ring_n = 0;
   // ... a launch of the Gram queue serves ring_members fits, and a third event follows its partial reduction (timers 0 and 6
@@ -78,25 +78,25 @@ struct kp_ctx {
   hipEvent_t ring_red[64] = {};
   int ring_members[64] = {};
   bool ring_has_red[64] = {};
-  bool solve_chained = false;   // set by a Gram launch that already made the solve stream wait for it
-  int part_flip = 0;
-  int reduce_timed_from = 1;   // evp index that marks the start of the last partial reduction
-  int* sticky_info = nullptr;       // device word: set by any deferred factorisation that hit a non-positive pivot
+  // ---- end of the pipelined fits' state ----
+  kp_comm_state* comm = nullptr;      // set by kp_comm_create: rank / world / RCCL communicator
+  std::atomic<bool> comm_abandoned{false};   // kp_comm_abandon: a bootstrap still blocked in another thread must not publish `comm`
+  bool gc_preloaded = false;          // kp_multi_fit_sharded: ctx->GC already holds the summed [G | C] of all devices - kp_fit skips its Gram launch
+  bool reduce_grams = false;          // kp_fit_sharded: all-reduce [G | C] over the ranks between the Gram kernel and the solve
   bool test_hooks = false;          // KP_TEST_HOOKS was set when the context was created: kp_fit honours KP_RANK_HINT_TEST (tests only)
   void* pin_scratch = nullptr;      // growable page-locked host scratch (kp_pinned_scratch): small results read back by direct DMA
   size_t pin_scratch_bytes = 0;
   double* pin_small = nullptr;      // 64 bytes of page-locked host memory: small results (info word + pivot ratio) come back in ONE direct DMA
-  int reserve_cus = 0;              // CUs left free by the Gram grid so the solve of the previous fit can run beside it
   int num_cu = 0;
   int64_t hbm_bytes = 0;
   std::string name;
   mutable std::string err;
-  double timers[19] = {0};            // (18: entry, workgroup order and copies of the most recent batched solve, not a time; kp_fit.hip; 17: which panel kernel and substitution form the most recent rank-revealing solve ran, not a time; kp_pivchol.hip; 16: power-table entries per raw value written by the in-loop build of the last Kronecker Gram launch, 3 or 4; 15: jobs of the last Kronecker Gram launch's plan that span two A groups; kp_gram3.hip; 12: the group size of the Gram queue, 13: fits served by the launches of timer 7; kp_fit.hip; 14: kernel code of the most recent sweep call, not a time; kp_batch.hip)
+  double timers[19] = {0};            // (18: entry, workgroup order and copies of the most recent batched solve, not a time; kp_solve.hip; 17: which panel kernel and substitution form the most recent rank-revealing solve ran, not a time; kp_pivchol.hip; 16: power-table entries per raw value written by the in-loop build of the last Kronecker Gram launch, 3 or 4; 15: jobs of the last Kronecker Gram launch's plan that span two A groups; kp_gram3.hip; 12: the group size of the Gram queue, 13: fits served by the launches of timer 7; kp_fit.hip; 14: kernel code of the most recent sweep call, not a time; kp_batch.hip)
   double gram_flops_per_pair = 0;
   // growable device workspaces
   void* ws[21] = {nullptr};     // slot 8: staging of the collectives, 9: rank-revealing solve, 10 / 11: Grams of the shadow dictionary of a dim_red fit, their half-transformed form
   size_t ws_bytes[21] = {0};   // 12 / 13: column states and results of the lasso homotopy (kp_lasso_path.hip); 14: econ-lifted rows of a dim_red fit (kp_gram3.hip)
-                                // 15 / 16: lifted snapshot panels of a wide dictionary, 17: split partials of its products, 18: scratch of the blocked factorisation (kp_wide.hip, kp_fit.hip)
+                                // 15 / 16: lifted snapshot panels of a wide dictionary, 17: split partials of its products, 18: scratch of the blocked factorisation (kp_wide.hip, kp_solve.hip)
                                 // 20: inputs, per-row blocks and results of the batched load observer (kp_observer.hip)
   int last_rank = -1;           // rank found by the most recent solve (W when the Gram matrix was positive definite)
   double last_pivot_ratio = 1.0; // min_i L_ii^2 / G_ii of the most recent synchronous least-squares solve (~1 / cond(G))
@@ -333,7 +333,6 @@ int kp_gram5_launch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s, d
 inline int kp_gram_dispatch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s, double* GC_dev, bool cover = false) {
   if (s->Ns > 0 && (!s->alpha || !s->beta || (s->m > 0 && !s->u)))    // an object whose refill failed part-way (kp_snapshots_update)
     return ctx->fail(KP_ERR_ARG, "kp_fit: the snapshot object holds no device arrays (a failed kp_snapshots_update?)");
-  ctx->reduce_timed_from = 1;
   KP_HIP(ctx, kp_snaps_acquire(s, ctx->stream));
   const int rc = kp_gram3_applicable(basis)   ? kp_gram3_launch(ctx, basis, s, GC_dev, cover)
                  : kp_gram_congruence_applicable(basis) ? kp_gram_congruence_launch(ctx, basis, s, GC_dev)
@@ -348,7 +347,7 @@ inline int kp_gram_dispatch(kp_ctx* ctx, const kp_basis* basis, const kp_snapsho
 // kp_chol_ll.hip: left-looking single-workgroup Cholesky for n <= 352 (in place, lower triangle; `info` as kp_chol_kernel)
 bool kp_chol_ll_applicable(int n);
 hipError_t kp_chol_ll_launch(double* Gp, int n, int nb, int* info, int* sticky, int prof, hipStream_t st, const double* thr = nullptr);
-// substitution with a factor the caller already holds (kp_fit.hip)
+// substitution with a factor the caller already holds (kp_solve.hip)
 int kp_factor_substitute_dev(kp_ctx* ctx, double* Lp, int n, double* Cp, int ncp, double* Dinv, hipStream_t st, int* form = nullptr);
 int kp_copy_to_host_async(kp_ctx* ctx, const void* src_dev, void* dst_host, size_t bytes, int mapped, hipStream_t s);
 int kp_pivchol_solve_dev(kp_ctx* ctx, const double* G_dev, const double* C_dev, int W, int ncols, double* K_dev, int* rank, int rank_hint = 0,
@@ -366,17 +365,21 @@ int kp_lift_dev(kp_ctx* ctx, const kp_basis* basis, int what, const double* dz, 
 int kp_lift_dev_ld(kp_ctx* ctx, const kp_basis* basis, int what, const double* dz, const double* du, int64_t rows, int64_t ldi, double* dout, int64_t ldo);
 // dictionaries too wide for the LDS-staged Gram kernels: lifted panels in HBM + TN products on the matrix pipe (kp_wide.hip)
 int kp_gram_wide_launch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s, double* GC_dev);
-int kp_chol_solve_dev(kp_ctx* ctx, double* G_dev, double* C_dev, int W, int ncols, double* K_dev, hipStream_t st = nullptr,
-                      hipEvent_t pad_done = nullptr, int* sticky = nullptr);
+// The dense solver (kp_solve.hip).  Systems up to KP_NARROW_NMAX (padded) are factored by one workgroup and substituted by
+// kp_trsm2_kernel; wider ones take the blocked path over all CUs, one system at a time.
+#define KP_NARROW_NMAX 512
+int kp_chol_solve_dev(kp_ctx* ctx, double* G_dev, double* C_dev, int W, int ncols, double* K_dev, hipStream_t st = nullptr, int* sticky = nullptr);
+// the info word and pivot ratio of the kp_chol_solve_dev that ran last on `st` (phases: kp_solve.hip)
+int kp_read_chol_info(kp_ctx* ctx, int W, int ncols, int* bad, const double* G_dev = nullptr, hipStream_t st = nullptr, int phase = 0);
 // Where kp_chol_solve_dev leaves its info word (non-zero: a non-positive pivot) in workspace 5, behind the padded copies of
-// G (np x np), C (np x ncp) and the inverted diagonal blocks: the ONE place that knows the layout (kp_fit.hip, kp_lasso.hip and
+// G (np x np), C (np x ncp) and the inverted diagonal blocks: the ONE place that knows the layout (kp_solve.hip, kp_lasso.hip and
 // kp_more.hip read the word through it).
 inline size_t kp_chol_info_offset(int W, int ncols) {
   const size_t np = (size_t)(W + 15) / 16 * 16, ncp = (size_t)(ncols + 15) / 16 * 16;
   return np * np * 8 + np * ncp * 8 + (np / 16) * 256 * 8;
 }
 int kp_chol_solve_batch_dev(kp_ctx* ctx, const double* G_dev, const double* C_dev, int W, int ncols, int nb, size_t gc_stride, double* K_dev,
-                            int k_first, int k_cap, hipStream_t st, hipEvent_t pad_done, int* sticky);
+                            int k_first, int k_cap, hipStream_t st, int* sticky);
 // least-squares solution, PSD guard and Lipschitz constant shared by all lasso values of one fit (kp_lasso.hip)
 struct kp_lasso_prep {
   bool ready = false;

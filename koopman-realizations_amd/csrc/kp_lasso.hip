@@ -710,7 +710,7 @@ static int lasso_copies(kp_ctx* ctx, hipStream_t s, std::vector<std::pair<const 
   return KP_OK;
 }
 
-// (kp_fit.hip) smallest pivot of the factorisation at the head of workspace 5 relative to its diagonal entry: ~1 / cond(G)
+// (kp_solve.hip) smallest pivot of the factorisation at the head of workspace 5 relative to its diagonal entry: ~1 / cond(G)
 __global__ void kp_pivot_ratio_kernel(const double* __restrict__ Lp, int n, const double* __restrict__ G, int W, double* __restrict__ out,
                                       const int* __restrict__ info, double* host_out);
 

@@ -117,7 +117,6 @@ extern "C" int kp_fit_refine(kp_ctx* ctx, const kp_basis* basis, const kp_snapsh
   double *Px = (double*)ws, *Py = (double*)(ws + bP), *E = (double*)(ws + 2 * bP);
   double *GC = (double*)(ws + 3 * bP), *Kd = GC + 2 * (size_t)W * W, *R = Kd + (size_t)W * W, *dK = R + (size_t)W * W;
   hipStream_t s = ctx->stream;
-  ctx->reserve_cus = 0;
   int rc = kp_gram_dispatch(ctx, basis, snaps, GC);
   if (rc) return rc;
   rc = kp_lift_dev(ctx, basis, KP_LIFT_ROW, snaps->alpha, snaps->u, Ns, Px);

@@ -1,4 +1,4 @@
-// Workgroup order of the batched block substitution (kp_fit.hip: kp_trsm2_batch_kernel), host and device.
+// Workgroup order of the batched block substitution (kp_solve.hip: kp_trsm2_batch_kernel), host and device.
 //
 // A system's ncb workgroups (one per block of 16 right-hand sides) all read that system's factor L.  The dispatcher hands
 // consecutive workgroup ids to the chip's KP_SOLVE_XCDS dies in turn, each with an L2 of its own: a grid whose x index is the

@@ -259,8 +259,8 @@ def test_fit_synthetic_config2(ctx):
 
 
 def test_async_fit_pipeline_matches_synchronous_result(ctx):
-    """kp_fit with K_out = NULL is asynchronous (solve of fit i overlaps the Gram of fit i+1 on a
-    second stream); results and error reporting must equal the synchronous path."""
+    """kp_fit with K_out = NULL is asynchronous (the fit is queued, its solve deferred to a batched launch sequence on the
+    same stream); results and error reporting must equal the synchronous path."""
     dic = ko.build_dictionary("bilinear", 6, 3, ["poly"], [3])
     b = make_basis(ctx, dic)
     sets = [synth_pairs(20000, seed=20 + i) for i in range(3)] + [synth_pairs(23000, seed=30)]
@@ -270,8 +270,8 @@ def test_async_fit_pipeline_matches_synchronous_result(ctx):
     tol = lambda Kref: 1e-11 * np.abs(Kref).max()
     for s, Kref in zip(snaps, Ksync):           # one fit per batch: kp_fit_get_K synchronises, which closes the batch
         kra.fit(ctx, b, s, fetch=False)
-        # the async path leaves CUs free for the overlapped solve => different snapshot split, different
-        # (still fixed) summation order of the partial Grams: equal to rounding, not bitwise
+        # the async path plans its Gram launch with the dictionary's cover plan => different (still fixed) summation order
+        # of the partial Grams: equal to rounding, not bitwise
         assert np.abs(ctx.fit_result(0, W) - Kref).max() <= tol(Kref)
     # a batch of pipelined fits: EVERY K stays retrievable (ring of result slots), in issue order
     for s in snaps[:3]:
@@ -438,22 +438,40 @@ ctx.synchronize()
 for q in range(max(0, n_fits - n_slots), n_fits):
     K = ctx.fit_result(q, b.W)
     assert np.abs(K - Kref[q % 3]).max() <= 1e-11 * np.abs(Kref[q % 3]).max(), q
+print("TIMER18 %r" % ctx.timer(18))
+if len(sys.argv) > 4:
+    assert ctx.timer(18) == float(sys.argv[4]), (ctx.timer(18), sys.argv[4])
 print("LONE_OK")
 """
 
+_LONE_TIMER18 = {}   # (n_fits, n_slots) -> kp_timer_get(18) of the child that ran them with KP_SOLVE_BATCH=1
 
-@pytest.mark.parametrize("n_fits,n_slots,env", [(129, 200, {}), (257, 300, {}), (7, 128, {"KP_SOLVE_BATCH": "1"}), (5, 64, {"KP_SOLVE_BATCH": "3"})])
-def test_a_lone_queued_fit_lands_in_its_own_ring_slot(n_fits, n_slots, env):
-    """A flush of exactly ONE queued fit at a non-zero ring position (129 pipelined fits with a 128-fit solve batch; a solve
-    batch of 1) takes the one-system TRSM, which writes K in place: it must apply the ring offset itself - three distinct
-    snapshot sets in rotation, so a K written to slot 0 (or left stale) is seen."""
+
+def _lone_fit_child(n_fits, n_slots, env, *expect_timer18):
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-c", _LONE_FIT_SCRIPT, root, str(n_fits), str(n_slots)], capture_output=True, text=True, timeout=300,
-                       env=dict(os.environ, **env))
+    r = subprocess.run([sys.executable, "-c", _LONE_FIT_SCRIPT, root, str(n_fits), str(n_slots), *[repr(v) for v in expect_timer18]], capture_output=True,
+                       text=True, timeout=300, env=dict(os.environ, **env))
     assert r.returncode == 0 and "LONE_OK" in r.stdout, r.stdout[-1500:] + r.stderr[-1500:]
+    if env.get("KP_SOLVE_BATCH") == "1":
+        _LONE_TIMER18[(n_fits, n_slots)] = float(r.stdout.split("TIMER18 ")[1].split()[0])
+
+
+@pytest.mark.parametrize("n_fits,n_slots,env", [(129, 200, {}), (257, 300, {}), (7, 128, {"KP_SOLVE_BATCH": "1"}), (5, 64, {"KP_SOLVE_BATCH": "3"}),
+                                                (4, 64, {"KP_SOLVE_BATCH": "0"})])
+def test_a_lone_queued_fit_lands_in_its_own_ring_slot(n_fits, n_slots, env):
+    """A flush of exactly ONE queued fit at a non-zero ring position (129 pipelined fits with a 128-fit solve batch; a solve
+    batch of 1) takes the one-system TRSM, which writes K in place: it must apply the ring offset itself - three distinct
+    snapshot sets in rotation, so a K written to slot 0 (or left stale) is seen.  KP_SOLVE_BATCH=0 is a batch of one as well:
+    its child also asserts that kp_timer_get(18) reads what the same fits leave with KP_SOLVE_BATCH=1."""
+    if env.get("KP_SOLVE_BATCH") == "0":
+        if (n_fits, n_slots) not in _LONE_TIMER18:
+            _lone_fit_child(n_fits, n_slots, {"KP_SOLVE_BATCH": "1"})
+        _lone_fit_child(n_fits, n_slots, env, _LONE_TIMER18[(n_fits, n_slots)])
+    else:
+        _lone_fit_child(n_fits, n_slots, env)
 
 
 _GRAM6_SCRIPT = r"""

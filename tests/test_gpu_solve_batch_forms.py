@@ -1,4 +1,4 @@
-"""GPU tests of the two forms of the batched solve of pipelined fits (kp_fit.hip: kp_chol_solve_batch_dev, nb > 1).
+"""GPU tests of the two forms of the batched solve of pipelined fits (kp_solve.hip: kp_chol_solve_batch_dev, nb > 1).
 
 KP_SOLVE_BATCH_FORM unset (or 1): systems up to n = 384 are substituted by kp_trsm2_batch_kernel - six row blocks per wave and
 two workgroups per CU, a flat grid in kp_solve_xcd_map order (a system's column blocks on one die), C read from the [G | C] ring
@@ -114,7 +114,7 @@ print("SOLVE_FORMS_CHILD_OK")
 
 
 def _child(out, form):
-    env = {k: v for k, v in os.environ.items() if k not in ("KP_SOLVE_BATCH_FORM", "KP_SOLVE_BATCH", "KP_TRSM_OLD", "KP_NO_ASYNC", "KP_GRAM_GROUP")}
+    env = {k: v for k, v in os.environ.items() if k not in ("KP_SOLVE_BATCH_FORM", "KP_SOLVE_BATCH", "KP_NO_ASYNC", "KP_GRAM_GROUP")}
     if form is not None:
         env["KP_SOLVE_BATCH_FORM"] = str(form)
     r = subprocess.run([sys.executable, "-c", _CHILD, ROOT, out], capture_output=True, text=True, timeout=300, env=env)

@@ -2,7 +2,7 @@
 arm's six states gives 728 functions (Ksysid.m:694-731; linear row 738 columns, bilinear row 2 940), poly-3 on a
 delay-embedded state 816 (Ksysid.m:868-907) - and `K = Px \\ Py` on them (Ksysid.m:1069).  Device side: lifted panels in HBM +
 TN products on the matrix pipe (csrc/kp_wide.hip, kp_tn_gemm.h), blocked Cholesky / substitution over all CUs
-(csrc/kp_fit.hip `chol_solve_wide`).  Oracle: oracle/koopman_oracle.py on the same inputs.  Tolerances (f64):
+(csrc/kp_solve.hip `chol_solve_wide`).  Oracle: oracle/koopman_oracle.py on the same inputs.  Tolerances (f64):
   G, C   1e-12 relative to max|G|
   K      max(1e-9, 50 cond(Px)^2 eps) relative to max|K| against the SVD least-squares oracle (normal equations)
   solve  residual |G K - C| <= 1e-11 |G| |K| against a dense numpy solve on random SPD systems

@@ -1,5 +1,5 @@
 #!/bin/bash
-# kernel timeline of the pipelined fit loop: gaps on the Gram stream and the overlap with the solve stream
+# kernel timeline of the pipelined fit loop: gaps on the Gram stream between the Gram kernels, their reductions and the batched solves
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/timeline
 rm -rf $O; mkdir -p $O

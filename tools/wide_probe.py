@@ -1,4 +1,4 @@
-"""Wide dictionaries (W > 512: lifted panels + TN products, blocked Cholesky; csrc/kp_wide.hip, kp_fit.hip): time of the Gram
+"""Wide dictionaries (W > 512: lifted panels + TN products, blocked Cholesky; csrc/kp_wide.hip, kp_solve.hip): time of the Gram
 pass and of one synchronous fit for the fourier dictionary of `def_fourierLift` on six states (Ksysid.m:694-731; linear W = 738,
 bilinear W = 2 940) at the arm data set's size and at 1e5 pairs, and of the solve alone on random SPD systems."""
 import os, sys, time
