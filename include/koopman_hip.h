@@ -151,7 +151,12 @@ int kp_basis_desc_dims(const kp_basis_desc* desc, int* nvars, int* nfull, int* N
  * get_econ_observables (Ksysid.m:1498) - principal
  * axes = eigenvectors of the covariance of the lifted snapshots, which kp_fit_gram provides without forming the lifted
  * matrix (the dictionary's constant column carries the column sums).  Eigenvalues are returned UNSORTED (lam[i]
- * belongs to column i of V); sweeps (may be NULL) receives the number of Jacobi sweeps. */
+ * belongs to column i of V); sweeps (may be NULL) receives the number of Jacobi sweeps.  Any symmetric matrix, not only a
+ * covariance: indefinite, singular, zero, with a zero diagonal, at any scale - a sweep counts as converged when every
+ * off-diagonal entry it met was at most 1e-15 of the largest |S_ij| of the input.  At most 30 sweeps are run.  A flat
+ * spectrum (clusters of equal eigenvalues) keeps rotating rounding noise of the size of that threshold inside a cluster and
+ * may use many or all of them; the decomposition is then as accurate as a converged one (the noise IS the off-diagonal
+ * mass), so the return value is KP_OK either way and `sweeps` = 30 is how a caller sees that the cap was reached. */
 int kp_sym_eig(kp_ctx* ctx, const double* S, int n, double* V_out, double* lam_out, int* sweeps);
 
 /* ---- lifting ----------------------------------------------------------------------
@@ -325,7 +330,9 @@ int kp_model_project_batch(kp_ctx* ctx, const double* K, const double* G, const 
  * val_model (Ksysid.m:1678-1689) z+ = A z + B u ; val_BLmodel (:1772-1787)
  * z+ = A z + B kron(I_m,z) u.  z0: N, U: T x m (rows = steps), Y: T x n_out with
  * Y(1,:) = Cz0 ... (C = first n_out entries of z, Ksysid.m:1203).  batch independent
- * models may be rolled out at once (arrays back to back). */
+ * models may be rolled out at once (arrays back to back).  m = 0 is a model without inputs and gives the trajectory of
+ * z+ = A z: B and U are then empty, but their pointers must still not be NULL (nothing is read through them).  Pipelined
+ * fits that are still queued are completed first, as by every entry point that shares the rollout's workspace. */
 int kp_rollout(kp_ctx* ctx, int model_type, int batch, const double* A, const double* B, int N, int m,
                const double* z0, const double* U, int T, int n_out, double* Y);
 

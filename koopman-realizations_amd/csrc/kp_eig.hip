@@ -20,8 +20,10 @@ __global__ __launch_bounds__(256) void kp_jacobi_eig_kernel(double* __restrict__
   const int np = ne / 2;
   for (int e = tid; e < n * n; e += 256) V[e] = (e % n == e / n) ? 1.0 : 0.0;
   {
+    // convergence scale: the largest entry of the WHOLE matrix (not of the diagonal alone - a matrix with a zero diagonal
+    // would be measured against the 1.0 of the zero matrix; for a covariance the two agree, |S_ij| <= max S_ii)
     double d = 0.0;
-    for (int i = tid; i < n; i += 256) d = fmax(d, fabs(S[i + (size_t)i * n]));
+    for (int e = tid; e < n * n; e += 256) d = fmax(d, fabs(S[e]));
     offmax[tid] = d;
     __syncthreads();
     for (int h = 128; h > 0; h >>= 1) {
@@ -143,8 +145,8 @@ __global__ __launch_bounds__(EIGM_NT) void kp_jacobi_eig_mw_kernel(double* __res
   const int np = ne / 2;
   for (int64_t e = gtid; e < (int64_t)n * n; e += gsize) V[e] = (e % n == e / n) ? 1.0 : 0.0;
   {
-    double d = 0.0;
-    for (int i = tid; i < n; i += EIGM_NT) d = fmax(d, fabs(S0[i + (size_t)i * n]));
+    double d = 0.0;                         // largest entry of the whole matrix, as in the one-workgroup form (every workgroup: the same value)
+    for (int e = tid; e < n * n; e += EIGM_NT) d = fmax(d, fabs(S0[e]));
     offmax[tid] = d;
     __syncthreads();
     for (int h = EIGM_NT / 2; h > 0; h >>= 1) {
@@ -259,7 +261,7 @@ extern "C" int kp_sym_eig(kp_ctx* ctx, const double* S, int n, double* V_out, do
   hipStream_t s = ctx->stream;
   KP_HIP(ctx, hipMemcpyAsync(dS, S, bS, hipMemcpyHostToDevice, s));
   KP_HIP(ctx, hipMemsetAsync(dsw, 0, 64, s));
-  // off-diagonal entries below 1e-15 of the largest diagonal entry are rounding noise of the rotations themselves: a
+  // off-diagonal entries below 1e-15 of the largest entry of S are rounding noise of the rotations themselves: a
   // threshold below that (1e-17 before) never triggers and every call ran all 30 sweeps
   static const bool one_wg = getenv("KP_EIG_ONE_WG") != nullptr;
   const bool multi = n > 40 && !one_wg && n <= EIGM_MAXN;

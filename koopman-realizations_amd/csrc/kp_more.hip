@@ -306,6 +306,10 @@ extern "C" int kp_rollout(kp_ctx* ctx, int model_type, int batch, const double* 
   if (model_type != KP_MODEL_LINEAR && model_type != KP_MODEL_BILINEAR)
     return ctx->fail(KP_ERR_ARG, "kp_rollout: linear or bilinear models only");
   KP_HIP(ctx, hipSetDevice(ctx->device));
+  if (ctx->async_pending) {   // queued pipelined fits first, as every other user of workspace slot 6 and of the event pair
+    int rc0 = kp_synchronize(ctx);
+    if (rc0) return rc0;
+  }
   const int bil = model_type == KP_MODEL_BILINEAR;
   const size_t mb = bil ? (size_t)N * m : (size_t)m;
   size_t nA = (size_t)batch * N * N, nB = (size_t)batch * N * mb, nz = (size_t)batch * N, nU = (size_t)batch * T * m,
@@ -315,7 +319,7 @@ extern "C" int kp_rollout(kp_ctx* ctx, int model_type, int batch, const double* 
   double *dA = ws, *dB = dA + nA, *dz = dB + nB, *dU = dz + nz, *dY = dU + nU;
   hipStream_t s = ctx->stream;
   KP_HIP(ctx, hipMemcpyAsync(dA, A, nA * 8, hipMemcpyHostToDevice, s));
-  KP_HIP(ctx, hipMemcpyAsync(dB, B, nB * 8, hipMemcpyHostToDevice, s));
+  if (nB) KP_HIP(ctx, hipMemcpyAsync(dB, B, nB * 8, hipMemcpyHostToDevice, s));   // m = 0: B and U are empty, z+ = A z
   KP_HIP(ctx, hipMemcpyAsync(dz, z0, nz * 8, hipMemcpyHostToDevice, s));
   if (nU) KP_HIP(ctx, hipMemcpyAsync(dU, U, nU * 8, hipMemcpyHostToDevice, s));
   KP_HIP(ctx, hipEventRecord(ctx->ev0, s));
