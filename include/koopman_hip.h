@@ -94,7 +94,8 @@ int kp_device_info(const kp_ctx* ctx, char* name, int name_len, int* num_cu, int
  * per CU, for padded widths up to 384.  X = 1: the workgroups of a system run on one die of the chip (csrc/kp_solve_xcd_map.h).  C = 1: the
  * right-hand sides are read from the [G | C] ring and K is stored into its slot of the result ring by the substitution itself -
  * no padded copy of C, no unpad launch.  211 or 100: the parts go together.  The results do not depend on it, bit for bit;
- * environment variable KP_SOLVE_BATCH_FORM=0 (read once) keeps the launch sequence of code 100 everywhere for A/B runs and tests. */
+ * environment variable KP_SOLVE_BATCH_FORM=0 (read once) keeps the launch sequence of code 100 everywhere for A/B runs and tests.
+ * 19: the kernel of the most recent batch of closed loops (koopman_hip_sim.h), ms. */
 int kp_timer_get(const kp_ctx* ctx, int which, double* ms);
 /* Device pointer + byte size of the library stream's raw handle, for profilers/benchmarks
  * that want to bracket work with their own HIP events: returns hipStream_t as void*. */

@@ -189,6 +189,12 @@ VALIDATE_CHUNK = 128               # KP_VALIDATE_CHUNK
 VALIDATE_CT_CHUNK = 32             # KP_VALIDATE_CT_CHUNK
 VALIDATE_CT_STAGE = 8192           # KP_VALIDATE_CT_STAGE
 
+# whole closed loops with the model as the plant (include/koopman_hip_sim.h)
+SIM_SIGNATURES = {
+    "kp_mpc_simulate": (C.c_int, [vp, vp, C.c_int, C.c_int, c_dp, C.c_int, c_dp, c_dp, C.c_int, c_dp, c_dp, c_dp, c_ip, c_ip]),
+}
+TIMER_MPC_SIM = 19                 # kp_timer_get slot: the kernel of the most recent kp_mpc_simulate, ms
+
 _lib = None
 
 
@@ -201,7 +207,7 @@ def lib():
                           "(make -C koopman-realizations_amd/csrc)")
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in (SIGNATURES | NMPC_SIGNATURES | OBSERVER_SIGNATURES | CT_SIGNATURES | ARM_SIGNATURES
-                                   | RSYS_SIGNATURES | VALIDATE_SIGNATURES).items():
+                                   | RSYS_SIGNATURES | VALIDATE_SIGNATURES | SIM_SIGNATURES).items():
             fn = getattr(l, name)
             fn.restype, fn.argtypes = res, args
         _lib = l

@@ -19,6 +19,7 @@
 #include <cstring>
 
 #include "kp_internal.h"
+#include "koopman_hip_sim.h"
 #include "kp_wg_inverse.h"
 #include <type_traits>
 
@@ -471,11 +472,19 @@ __device__ __forceinline__ bool mpc_load_observer(const MpcArgs& a, const MpcLoa
 // (its registers and branches cost the batch 1.8x when they were a run-time option).
 // LOADED: the load observer and the loaded lift in front (kp_mpc_step_loaded, la != nullptr); the other instantiations
 // carry none of its code.
-template <bool WARM, bool LOADED = false>
-__device__ __forceinline__ void mpc_step_body(const MpcArgs& a, const MpcLoadArgs* la = nullptr) {
+// SIM: one step of a device-resident closed loop (kp_mpc_sim_kernel, si != nullptr): zeta, u_prev and the reference window
+// are taken from LDS, where the loop keeps them, the solution goes to LDS and the P | PB block was staged by the caller.
+// Returns the step's status (0, or nonzero when a QP failed; uniform).
+struct MpcSimIn {
+  const double *zeta, *up, *yr;   // LDS: nzeta | m | (Np + 1) nproj
+  double* x;                      // LDS: the solution [u_0; u_1; ...] (nvar)
+  double* z;                      // set by the step: its lifted state (LDS, N), intact until the next step
+};
+template <bool WARM, bool LOADED = false, bool SIM = false>
+__device__ __forceinline__ int mpc_step_body(const MpcArgs& a, const MpcLoadArgs* la = nullptr, MpcSimIn* si = nullptr) {
   extern __shared__ __align__(16) double sm[];
   const int tid = threadIdx.x;
-  const int pb = blockIdx.x;
+  const int pb = SIM ? 0 : blockIdx.x;     // (SIM: the caller's pointers are the trial's own)
   const int N = a.N, m = a.m, Np = a.Np, nproj = a.nproj, nv = a.nvar, nr = a.nrows;
   // a.alias (batched launches, one linearisation pass): the assembly's inputs z | beta | S | e are dead once Hq and f
   // exist, which is before the solver's scratch is first written - they live in its second n x n block, and a problem
@@ -510,7 +519,14 @@ __device__ __forceinline__ void mpc_step_body(const MpcArgs& a, const MpcLoadArg
   // trip it was to hide behind, 32.6 against 31.7 us.)
   const double* zin = a.has_basis ? a.zeta + (size_t)pb * a.basis.nzeta : a.z + (size_t)pb * N;
   const int nzin = a.has_basis ? a.basis.nzeta : N, nyr = (Np + 1) * nproj;
-  {
+  if constexpr (SIM) {
+    // the loop's state is in LDS (the previous step's ordinary stores; an LDS-DMA from global memory is not ordered behind
+    // those): plain copies to the same three arrays, published by the barrier below
+    for (int e = tid; e < nzin; e += 256) z[e] = si->zeta[e];
+    for (int e = tid; e < nyr; e += 256) ev[e] = si->yr[e];
+    if (tid < m) f[tid] = si->up[tid];
+    si->z = z;
+  } else {
     typedef __attribute__((address_space(3))) char lds_char;
     typedef __attribute__((address_space(1))) const char glb_char;
     const int w_ = tid >> 6, l4 = (tid & 63) * 4;
@@ -545,7 +561,7 @@ __device__ __forceinline__ void mpc_step_body(const MpcArgs& a, const MpcLoadArg
   {
     // P | PB (constants of the model that every step reads once, 55 KB at N = 84) go to LDS by LDS-DMA while the host words
     // are on their way: no registers, nothing to wait for before the barrier below (hipcc drains vmcnt there)
-    if (a.stage_off) {
+    if (!SIM && a.stage_off) {            // (SIM: staged once, before the loop's first step)
       typedef __attribute__((address_space(3))) char lds_char;
       typedef __attribute__((address_space(1))) const char glb_char;
       lds_char* dst = (lds_char*)(sm + a.stage_off);
@@ -606,7 +622,7 @@ __device__ __forceinline__ void mpc_step_body(const MpcArgs& a, const MpcLoadArg
         for (int e = tid; e < nv * nv + nv + nr; e += 256) ex[e] = __builtin_nan("");
       }
       mpc_step_finish(a, pb, tid, 1, stamps);
-      return;
+      return 1;
     }
   }
   // ---- lifted state (Kmpc.m:842; loaded: Kmpc.m:839-840, Ksysid.m:1606-1612) ----
@@ -851,10 +867,10 @@ __device__ __forceinline__ void mpc_step_body(const MpcArgs& a, const MpcLoadArg
       for (int e = tid; e < nv; e += 256) ex[nv * nv + e] = f[e];
       for (int e = tid; e < nr; e += 256) ex[nv * nv + nv + e] = bq[e];
     }
-    if (a.assemble_only) return;                 // (uniform) H, f, b are in qp_export, z in z_out
+    if (a.assemble_only) return 0;               // (uniform) H, f, b are in qp_export, z in z_out
     // ---- QP by wave 0 ----
     if (stamps && tid == 0) stamps[3] = wall_clock64();
-    double* xout = a.U + (size_t)pb * nv;
+    double* xout = SIM ? si->x : a.U + (size_t)pb * nv;
     // H^-1 by the whole workgroup into the solver's scratch (first n*n doubles).  Hq is not needed after this
     // point (the solver works from H^-1; the next linearisation pass rebuilds it), so it is the second buffer of the
     // ping-pong inverse.
@@ -994,6 +1010,7 @@ __device__ __forceinline__ void mpc_step_body(const MpcArgs& a, const MpcLoadArg
       __hip_atomic_store(&a.done_flag[0], a.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
+  return status;
 }
 
 // Two entry points over the same body: the single-problem kernel (warm start, workgroup-wide solver) may use every register
@@ -1008,6 +1025,161 @@ __global__ __launch_bounds__(256) void kp_mpc_step_loaded_kernel(MpcArgs a, MpcL
 }
 __global__ __launch_bounds__(256, 4) void kp_mpc_step_batch_kernel(MpcArgs a) {
   mpc_step_body<false>(a);
+}
+
+// ---- whole closed loops with the model as the plant (kp_mpc_simulate; Kmpc.run_simulation, Kmpc.m:403-512) -----------
+// One workgroup per trial runs steps k = 1 .. nref - 1 of the loop in scaled units: lift of Y[k-1], the step against rows
+// k-1 .. k-1+Np of the reference (its last row repeated behind its end, :354-365, :473-477) with u_prev = U[k-1], then
+// U[k] = the solution's second row and Y[k] = (A z + B u_prev)[0:n] or (A z + sum_i u_prev,i B_i z)[0:n] (the one-step input
+// delay of :495-496; C = [I 0], and only those n rows are ever read: the next step lifts Y[k] again).  A failed QP ends
+// the trial (the break of :483-485).
+// Everything the loop carries lives in LDS behind the step's own block, at sim_off (offsets in doubles, each even):
+//   y n | u m | x nvar | ab (m + 1) n partial products of the model step | the reference with Np trailing copies of its last
+//   row ((nref + Np) nproj: every step's window is one contiguous block) | warm 1 + nvar ints: the trial's own optimal active
+//   set of the previous step | the dictionary's column descriptors | then P | PB at stage_off.
+// r and bq0 (m + nrows doubles) stay in global memory: a step asks for them with its first instructions and uses them
+// after the lift, as a single step does - nothing waits for them.
+// The step body takes these by plain LDS reads (its SIM mode): nothing that a step wrote is read through LDS-DMA.  No state
+// passes through global memory; U, Y and Z rows are only ever written.  A trial touches nothing that depends on blockIdx.x
+// except its own rows, so its result does not depend on nb or on its index.
+struct SimLayout {
+  int y, u, x, ab, ref, warm, cols, total;
+};
+__host__ __device__ inline SimLayout sim_layout(int n, int m, int nv, int nproj, int Np, int nref, int nfull) {
+  SimLayout L;
+  int o = 0;
+  L.y = o; o += even_up(n);
+  L.u = o; o += even_up(m);
+  L.x = o; o += even_up(nv);
+  L.ab = o; o += even_up((m + 1) * n);
+  L.ref = o; o += even_up((nref + Np) * nproj);
+  L.warm = o; o += even_up((1 + nv + 1) / 2);
+  L.cols = o; o += 2 * nfull;               // ColDesc: 16 bytes
+  L.total = o;
+  return L;
+}
+struct MpcSimArgs {
+  int nref, n, ref_shared, sim_off;
+  const double *ref, *y0, *u0;      // [nb or 1][nref][nproj], [nb][n], [nb][m]
+  double *U, *Y, *Z;                // [nb][nref][m], [nb][nref][n], [nb][nref - 1][N] or nullptr
+  int *steps_done, *status;         // [nb]
+};
+__global__ __launch_bounds__(256) void kp_mpc_sim_kernel(MpcArgs a, MpcSimArgs sa) {
+  extern __shared__ __align__(16) double sm[];
+  const int tid = threadIdx.x;
+  const size_t trial = blockIdx.x;
+  const int N = a.N, m = a.m, Np = a.Np, nproj = a.nproj, nv = a.nvar, n = sa.n, nref = sa.nref;
+  const int nfull = a.basis.nfull;
+  const SimLayout L = sim_layout(n, m, nv, nproj, Np, nref, nfull);
+  double* sb = sm + sa.sim_off;
+  double* y = sb + L.y;
+  double* u = sb + L.u;
+  double* ab = sb + L.ab;
+  double* refl = sb + L.ref;
+  int* warm = (int*)(sb + L.warm);
+  ColDesc* cols = (ColDesc*)(sb + L.cols);
+  double* Ut = sa.U + trial * (size_t)nref * m;
+  double* Yt = sa.Y + trial * (size_t)nref * n;
+  double* Zt = sa.Z ? sa.Z + trial * (size_t)(nref - 1) * N : nullptr;
+  // ---- once per trial: what is constant over the run, the staged reference and row 0 ----
+  if (a.stage_off) {          // P | PB by LDS-DMA, as a single step stages it
+    typedef __attribute__((address_space(3))) char lds_char;
+    typedef __attribute__((address_space(1))) const char glb_char;
+    lds_char* dst = (lds_char*)(sm + a.stage_off);
+    glb_char* src = (glb_char*)a.P;
+    const int wbase = (tid & ~63) * 16, lane16 = (tid & 63) * 16;
+    for (int o = wbase; o < a.stage_doubles * 8; o += 256 * 16)
+      __builtin_amdgcn_global_load_lds(src + o + lane16, dst + o, 16, 0, 0);
+  }
+  {
+    const double* rt = sa.ref + (sa.ref_shared ? 0 : trial * (size_t)nref * nproj);
+    for (int e = tid; e < (nref + Np) * nproj; e += 256) {
+      const int row = e / nproj, p = e - row * nproj;
+      refl[e] = rt[(size_t)min(row, nref - 1) * nproj + p];
+    }
+    for (int e = tid; e < n; e += 256) {
+      const double v = sa.y0[trial * n + e];
+      y[e] = v;
+      Yt[e] = v;
+    }
+    for (int e = tid; e < m; e += 256) {
+      const double v = sa.u0[trial * m + e];
+      u[e] = v;
+      Ut[e] = v;
+    }
+    for (int e = tid; e < nfull; e += 256) cols[e] = a.basis.cols[e];
+    // cold first step: an empty set - and row ids of 0 behind it: a step asks for the constraint rows of ALL nvar ids before
+    // it knows the set's size (mpc_step_body: warm_row, then ell.val[k nrows + warm_row]), and LDS starts out as garbage
+    if (tid <= nv) warm[tid] = 0;           // (nvar <= 64)
+  }
+  // the LDS-DMA above is counted by the vector-memory counter, which a barrier does not wait for by itself
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  MpcArgs s = a;
+  s.basis.cols = cols;
+  s.warm = warm;
+  s.status = sa.status + trial;
+  MpcSimIn si;
+  si.zeta = y;
+  si.up = u;
+  si.x = sb + L.x;
+  si.z = sm;
+  const bool bil = a.model_type == KP_MODEL_BILINEAR;
+  const double qnan = __builtin_nan("");
+  int k = 1, failed = 0;
+  for (; k < nref; ++k) {
+    si.yr = refl + (size_t)(k - 1) * nproj;
+    s.z_out = Zt ? Zt + (size_t)(k - 1) * N : nullptr;
+    failed = mpc_step_body<true, false, true>(s, nullptr, &si);     // (ends behind a barrier: x, z and the status are visible)
+    if (failed) break;                      // (uniform)
+    // model step, rows 0 .. n-1: ab[j n + r] = row r of A (j = 0) or of B_j (bilinear, j = 1 .. m) times z, four lanes each
+    const double* z = si.z;
+    const int nterm = (bil ? m + 1 : 1) * n;
+    for (int e4 = tid; e4 < nterm * 4; e4 += 256) {
+      const int e = e4 >> 2, part = e4 & 3;
+      const int j = e / n, r = e - j * n;
+      const double* Mr = (j == 0 ? a.A : a.B + (size_t)(j - 1) * N * N) + r;
+      double t = 0.0;
+      for (int c = part; c < N; c += 4) t += Mr[(size_t)c * N] * z[c];
+      t += __shfl_xor(t, 1, 64);
+      t += __shfl_xor(t, 2, 64);
+      if (part == 0) ab[e] = t;
+    }
+    __syncthreads();
+    double ynew = 0.0, unew = 0.0;
+    if (tid < n) {
+      ynew = ab[tid];
+      // (two loops where one conditional expression would do: see the compiler hazard in DESIGN 3.3h - with the single
+      //  expression the hipcc of ROCm 7.2 places its copy of the LDS aperture register in VCC and stops with "Illegal
+      //  instruction detected"; a build failure, never wrong code)
+      if (bil)
+        for (int i = 0; i < m; ++i) ynew += ab[(i + 1) * n + tid] * u[i];
+      else
+        for (int i = 0; i < m; ++i) ynew += a.B[tid + (size_t)i * N] * u[i];
+    }
+    if (tid < m) unew = si.x[m + tid];      // the second row of the solution
+    __syncthreads();                        // (every read of the old u is done)
+    if (tid < n) {
+      y[tid] = ynew;
+      Yt[(size_t)k * n + tid] = ynew;
+    }
+    if (tid < m) {
+      u[tid] = unew;
+      Ut[(size_t)k * m + tid] = unew;
+    }
+    __syncthreads();                        // y, u and the body's arrays are free for the next step
+  }
+  if (failed) {
+    // rows k .. nref-1 of U and Y and the lifted states from this step's on: NaN (the step wrote its z behind a barrier)
+    for (size_t e = (size_t)k * m + tid; e < (size_t)nref * m; e += 256) Ut[e] = qnan;
+    for (size_t e = (size_t)k * n + tid; e < (size_t)nref * n; e += 256) Yt[e] = qnan;
+    if (Zt)
+      for (size_t e = (size_t)(k - 1) * N + tid; e < (size_t)(nref - 1) * N; e += 256) Zt[e] = qnan;
+  }
+  if (tid == 0) {
+    sa.steps_done[trial] = k - 1;
+    sa.status[trial] = failed ? KP_ERR_QP_FAIL : KP_OK;
+  }
 }
 
 // ---- host API ------------------------------------------------------------------------------------
@@ -1587,6 +1759,115 @@ extern "C" int kp_mpc_step_batch(kp_mpc* M, int nb, const double* z, const doubl
                                  int* status) {
   if (!M) return KP_ERR_ARG;
   return mpc_run(M, nullptr, nb, z, nullptr, u_prev, Yr, 1, U_out, nullptr, status);
+}
+
+// Whole closed loops, one workgroup per trial (kp_mpc_sim_kernel).  Small calls (a single trial of a few hundred steps)
+// are latency bound: inputs and outputs each cross in ONE copy through the page-locked scratch.  Large batches are
+// bandwidth bound: their outputs go straight to the caller's arrays instead of through a second host copy.
+#define KP_SIM_PINNED_BYTES ((size_t)4 << 20)
+extern "C" int kp_mpc_simulate(kp_mpc* M, const kp_basis* basis, int nb, int nref, const double* ref, int ref_shared,
+                               const double* y0, const double* u0, int iters, double* U, double* Y, double* Z, int* steps_done,
+                               int* status) {
+  if (!M) return KP_ERR_ARG;
+  kp_ctx* ctx = M->ctx;
+  if (nb < 1 || nref < 1 || iters < 1)
+    return ctx->fail(KP_ERR_ARG, "kp_mpc_simulate: nb, nref and iters must be at least 1 (nb = " + std::to_string(nb) + ", nref = " +
+                                     std::to_string(nref) + ", iters = " + std::to_string(iters) + ")");
+  if (!basis || !ref || !y0 || !u0 || !U || !Y || !steps_done || !status)
+    return ctx->fail(KP_ERR_ARG, "kp_mpc_simulate: NULL argument (only Z may be NULL)");
+  const BasisDev& b = basis->dev;
+  if (b.model_type == KP_MODEL_NONLINEAR) return ctx->fail(KP_ERR_ARG, "kp_mpc_simulate: the dictionary of a nonlinear model");
+  if (b.N != M->N)
+    return ctx->fail(KP_ERR_ARG, "kp_mpc_simulate: the dictionary lifts to N = " + std::to_string(b.N) + ", the controller's model has N = " +
+                                     std::to_string(M->N) + " (a loaded controller, N (nw + 1), has no such loop)");
+  if (M->sb_n > 0)
+    return ctx->fail(KP_ERR_ARG, "kp_mpc_simulate: the controller has state bounds (those steps go through the generic QP kernel)");
+  const int N = M->N, m = M->m, Np = M->Np, nproj = M->nproj, nv = M->nvar, nr = M->nrows, n = b.nzeta;
+  if (Np < 2) return ctx->fail(KP_ERR_ARG, "kp_mpc_simulate: the loop applies the second row of the solution: horizon >= 2");
+  if (n > N || n > 256) return ctx->fail(KP_ERR_ARG, "kp_mpc_simulate: nzeta = " + std::to_string(n) + " exceeds N or 256");
+  if (iters > 1 && M->model_type != KP_MODEL_BILINEAR) iters = 1;
+  KP_HIP(ctx, hipSetDevice(ctx->device));
+  if (ctx->async_pending) {
+    int rc0 = kp_synchronize(ctx);
+    if (rc0) return rc0;
+  }
+  // LDS: the step's block | the loop's block | P | PB when it still fits
+  size_t lds = (size_t)mpc_lds_doubles(N, m, Np, nproj, nv, nr, iters, b.nfull) * 8 + 32;
+  const SimLayout L = sim_layout(n, m, nv, nproj, Np, nref, b.nfull);
+  MpcSimArgs sa{};
+  sa.sim_off = (int)((lds / 8 + 1) & ~(size_t)1);
+  const size_t lds_need = ((size_t)sa.sim_off + (size_t)L.total) * 8;
+  if (lds_need > 160 * 1024)
+    return ctx->fail(KP_ERR_ARG, "kp_mpc_simulate: the step and a reference of " + std::to_string(nref) + " rows need " +
+                                     std::to_string(lds_need) + " bytes of LDS (163840 at most)");
+  lds = lds_need;
+  MpcArgs a{};
+  a.basis = b;
+  a.has_basis = 1;
+  a.model_type = M->model_type; a.N = N; a.m = m; a.Np = Np; a.nproj = nproj; a.nvar = nv; a.nrows = nr; a.iters = iters;
+  a.q_run = M->q_run; a.q_term = M->q_term;
+  a.A = M->A; a.B = M->B; a.P = M->P; a.S0 = M->S0; a.PB = M->PB; a.r = M->r; a.Aq = M->Aq; a.bq0 = M->bq0; a.Anorm = M->Anorm;
+  a.ell = EllMat{M->ellv, M->ellc, M->Anorm, M->ellK};
+  a.qp_wg = 1;
+  a.stage_off = 0;
+  a.stage_doubles = M->stage_doubles;
+  if (lds + 16 + (size_t)M->stage_doubles * 8 <= 160 * 1024) {
+    a.stage_off = (int)((lds / 8 + 1) & ~(size_t)1);
+    lds = (size_t)(a.stage_off + M->stage_doubles) * 8;
+  }
+  // device block: [ref | y0 | u0] | U | Y | Z | steps_done, status
+  const size_t nR = (size_t)(ref_shared ? 1 : nb) * nref * nproj, nY0 = (size_t)nb * n, nU0 = (size_t)nb * m, n_in = nR + nY0 + nU0;
+  const size_t nU = (size_t)nb * nref * m, nY = (size_t)nb * nref * n, nZ = Z ? (size_t)nb * (nref - 1) * N : 0;
+  const size_t n_int = ((size_t)2 * nb + 1) / 2, n_out = nU + nY + nZ + n_int;
+  double* ws = (double*)ctx->workspace(6, (n_in + n_out) * 8);
+  if (!ws) return ctx->fail(KP_ERR_HIP, "kp_mpc_simulate: out of device memory");
+  const bool pinned = (n_in + n_out) * 8 <= KP_SIM_PINNED_BYTES;
+  std::vector<double> h_vec;
+  double* h = nullptr;
+  if (pinned) {
+    h = (double*)kp_pinned_scratch(ctx, (n_in + n_out) * 8);
+    if (!h) return ctx->fail(KP_ERR_HIP, "kp_mpc_simulate: out of page-locked memory");
+  } else {
+    h_vec.resize(n_in);
+    h = h_vec.data();
+  }
+  memcpy(h, ref, nR * 8);
+  memcpy(h + nR, y0, nY0 * 8);
+  memcpy(h + nR + nY0, u0, nU0 * 8);
+  hipStream_t s = ctx->stream;
+  KP_HIP(ctx, hipMemcpyAsync(ws, h, n_in * 8, hipMemcpyHostToDevice, s));
+  double* d_out = ws + n_in;
+  sa.nref = nref; sa.n = n; sa.ref_shared = ref_shared ? 1 : 0;
+  sa.ref = ws; sa.y0 = ws + nR; sa.u0 = ws + nR + nY0;
+  sa.U = d_out; sa.Y = d_out + nU; sa.Z = nZ ? d_out + nU + nY : nullptr;
+  sa.steps_done = (int*)(d_out + nU + nY + nZ);
+  sa.status = sa.steps_done + nb;
+  static KpLdsCache sim_lds;
+  KP_HIP(ctx, kp_ensure_lds(sim_lds, (const void*)kp_mpc_sim_kernel, lds));
+  KP_HIP(ctx, hipEventRecord(ctx->evp[4], s));
+  hipLaunchKernelGGL(kp_mpc_sim_kernel, dim3(nb), dim3(256), lds, s, a, sa);
+  KP_HIP(ctx, hipGetLastError());
+  KP_HIP(ctx, hipEventRecord(ctx->evp[5], s));
+  if (pinned) {
+    double* h_out = h + n_in;
+    KP_HIP(ctx, hipMemcpyAsync(h_out, d_out, n_out * 8, hipMemcpyDeviceToHost, s));
+    KP_HIP(ctx, hipStreamSynchronize(s));
+    memcpy(U, h_out, nU * 8);
+    memcpy(Y, h_out + nU, nY * 8);
+    if (nZ) memcpy(Z, h_out + nU + nY, nZ * 8);
+    memcpy(steps_done, h_out + nU + nY + nZ, (size_t)nb * sizeof(int));
+    memcpy(status, (const int*)(h_out + nU + nY + nZ) + nb, (size_t)nb * sizeof(int));
+  } else {
+    KP_HIP(ctx, hipMemcpyAsync(U, sa.U, nU * 8, hipMemcpyDeviceToHost, s));
+    KP_HIP(ctx, hipMemcpyAsync(Y, sa.Y, nY * 8, hipMemcpyDeviceToHost, s));
+    if (nZ) KP_HIP(ctx, hipMemcpyAsync(Z, sa.Z, nZ * 8, hipMemcpyDeviceToHost, s));
+    KP_HIP(ctx, hipMemcpyAsync(steps_done, sa.steps_done, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s));
+    KP_HIP(ctx, hipMemcpyAsync(status, sa.status, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s));
+    KP_HIP(ctx, hipStreamSynchronize(s));
+  }
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, ctx->evp[4], ctx->evp[5]) == hipSuccess) ctx->timers[19] = ms;
+  return KP_OK;
 }
 
 extern "C" int kp_mpc_last_qp(kp_mpc* M, double* Hq, double* f, double* Aq, double* bq) {

@@ -843,6 +843,32 @@ class Mpc:
                                           st.ctypes.data_as(F.c_ip)), self.ctx.handle)
         return np.transpose(U, (0, 2, 1)), st
 
+    def simulate(self, basis: Basis, ref_sc, y0_sc, u0_sc, iters=1, want_Z=True):
+        """kp_mpc_simulate: nb closed loops with the model as the plant in one launch (Kmpc.run_simulation's loop, scaled
+        units).  ref_sc: (nref, nproj) for every trial or (nb, nref, nproj); y0_sc (nb, n), u0_sc (nb, m).  Returns
+        (U (nb, nref, m), Y (nb, nref, n), Z (nb, nref-1, N) or None, steps_done (nb,), status (nb,)); rows behind a failed
+        step are NaN.  The kernel time is ctx.timer(F.TIMER_MPC_SIM) afterwards, ms."""
+        y0 = np.ascontiguousarray(np.atleast_2d(y0_sc), dtype=np.float64)
+        u0 = np.ascontiguousarray(np.atleast_2d(u0_sc), dtype=np.float64)
+        ref = np.ascontiguousarray(ref_sc, dtype=np.float64)
+        nb, n = y0.shape
+        shared = ref.ndim == 2
+        if ref.ndim not in (2, 3) or ref.shape[-1] != self.nproj or (not shared and ref.shape[0] != nb):
+            raise ValueError(f"ref_sc must be (nref, {self.nproj}) or ({nb}, nref, {self.nproj}), not {ref.shape}")
+        if u0.shape != (nb, self.m):
+            raise ValueError(f"u0_sc must be ({nb}, {self.m}), not {u0.shape}")
+        if n != basis.nzeta:       # the library reads nzeta outputs per row: a model with delays is not this loop
+            raise F.KoopmanHipError(F.KP_ERR_ARG, f"kp_mpc_simulate: y0 has n = {n} entries, the dictionary's zeta has "
+                                                  f"{basis.nzeta} (models with delays have no such loop)")
+        nref = ref.shape[-2]
+        U = np.zeros((nb, nref, self.m)); Y = np.zeros((nb, nref, n))
+        Z = np.zeros((nb, max(nref - 1, 0), self.N)) if want_Z else None
+        sd = np.zeros(nb, dtype=np.int32); st = np.zeros(nb, dtype=np.int32)
+        F.check(F.lib().kp_mpc_simulate(self._h, basis._h, nb, nref, F.dptr(ref), 1 if shared else 0, F.dptr(y0), F.dptr(u0),
+                                        int(iters), F.dptr(U), F.dptr(Y), F.dptr(Z), sd.ctypes.data_as(F.c_ip),
+                                        st.ctypes.data_as(F.c_ip)), self.ctx.handle)
+        return U, Y, Z, sd, st
+
     def last_qp(self):
         """(Hq, f, Aq, bq) of the most recent single-problem step: quadprog(Hq, f, Aq, bq)."""
         Hq = np.zeros((self.nvar, self.nvar), order="F"); f = np.zeros(self.nvar)

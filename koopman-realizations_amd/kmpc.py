@@ -303,6 +303,67 @@ class Kmpc:
             k += 1
         return {k_: np.array(v) for k_, v in res.items()}
 
+    # ---- Kmpc.m:390-399 ---------------------------------------------------------------------------
+    def resample_ref(self, ref):
+        """The reference {t, y} resampled at the model's sampling time: tr = 0 : Ts : t(end), interp1(t, y, tr)."""
+        Ts = float(self.params["Ts"])
+        t = np.asarray(ref["t"], dtype=np.float64).reshape(-1)
+        y = np.asarray(ref["y"], dtype=np.float64)
+        y = y.reshape(-1, 1) if y.ndim == 1 else y
+        if y.shape[0] != t.size:
+            raise ValueError("ref['y'] must have one row per entry of ref['t']")
+        tr = np.arange(int(np.floor(t[-1] / Ts + 1e-9)) + 1) * Ts       # the colon's last element does not pass t(end)
+        return np.column_stack([np.interp(tr, t, y[:, j]) for j in range(y.shape[1])])
+
+    def run_simulations(self, refs, y0s=None, u0s=None):
+        """run_simulation for many trials in ONE launch (kp_mpc_simulate): the whole loop of every trial - lift, step, model
+        step - runs on the device, one workgroup per trial.  refs: one reference for every trial, or a list of them (all of
+        the same length once sampled at Ts); a reference is an array with a row per sample or a dict {t, y}, which goes
+        through resample_ref.  y0s / u0s: (trials, n) / (trials, m) initial outputs and inputs (None: zeros; one row serves
+        every trial).  Returns a list with one dict per trial: run_simulation's fields T, U, Y, K, R, Z scaled up, cut
+        behind the last completed step, steps_done, and comp_time = the kernel's time divided by the steps it ran, for
+        every step.  Models with delays, loaded models and controllers with state bounds have no device loop: they run
+        through run_simulation, trial by trial."""
+        p = self.params
+        n, m = p["n"], p["m"]
+        s = self.sysid
+        one = isinstance(refs, dict) or (not isinstance(refs, (list, tuple)) and np.ndim(refs) <= 2)
+        ref_list = [refs] if one else list(refs)
+        ref_list = [self.resample_ref(r) if isinstance(r, dict) else np.atleast_2d(np.asarray(r, dtype=np.float64)) for r in ref_list]
+        y0s = None if y0s is None else np.atleast_2d(np.asarray(y0s, dtype=np.float64))
+        u0s = None if u0s is None else np.atleast_2d(np.asarray(u0s, dtype=np.float64))
+        nb = max(len(ref_list), 1 if y0s is None else y0s.shape[0], 1 if u0s is None else u0s.shape[0])
+        for name, a in (("refs", ref_list), ("y0s", y0s), ("u0s", u0s)):
+            if a is not None and len(a) not in (1, nb):
+                raise ValueError(f"{name} has {len(a)} entries for {nb} trials")
+        y0s = np.zeros((nb, n)) if y0s is None else np.broadcast_to(y0s, (nb, n))
+        u0s = np.zeros((nb, m)) if u0s is None else np.broadcast_to(u0s, (nb, m))
+        if (self.model_type == "nonlinear" or self.loaded or self.state_bounds is not None or int(p.get("nd", 0)) > 0):
+            out = []
+            for i in range(nb):
+                r = self.run_simulation(ref_list[i if len(ref_list) > 1 else 0], y0s[i], u0s[i])
+                r["steps_done"] = len(r["K"]) - 1
+                out.append(r)
+            return out
+        nref = ref_list[0].shape[0]
+        if any(r.shape != ref_list[0].shape for r in ref_list):
+            raise ValueError("run_simulations: every reference must have the same number of rows")
+        ref_sc = self.scaledown_ref(ref_list[0]) if len(ref_list) == 1 else np.stack([self.scaledown_ref(r) for r in ref_list])
+        U, Y, Z, sd, st = self.dev.simulate(self.sysid.basis_dev, ref_sc, s.scaledown_y(y0s), s.scaledown_u(u0s), 1, True)
+        from . import _ffi as F
+        steps = int(sd.sum())
+        per_step = self.ctx.timer(F.TIMER_MPC_SIM) * 1e-3 / steps if steps else 0.0
+        out = []
+        for i in range(nb):
+            k = int(sd[i]) + 1                                         # rows 0 .. steps_done
+            rs = ref_sc if ref_sc.ndim == 2 else ref_sc[i]
+            R = np.vstack([ref_list[i if len(ref_list) > 1 else 0][:1], self.scaleup_ref(rs[:k - 1])]) if k > 1 else \
+                ref_list[i if len(ref_list) > 1 else 0][:1].copy()
+            out.append({"T": np.arange(k) * p["Ts"], "U": np.vstack([u0s[i:i + 1], s.scaleup_u(U[i, 1:k])]),
+                        "Y": np.vstack([y0s[i:i + 1], s.scaleup_y(Y[i, 1:k])]), "K": np.arange(k), "R": R,
+                        "Z": Z[i, :k - 1].copy(), "comp_time": np.full(k - 1, per_step), "steps_done": int(sd[i])})
+        return out
+
 
 class Ksim:
     """Closed-loop simulator (mirror of classdef Ksim, Ksim.m:1).  `system_class` must offer
