@@ -95,7 +95,12 @@ int kp_device_info(const kp_ctx* ctx, char* name, int name_len, int* num_cu, int
  * right-hand sides are read from the [G | C] ring and K is stored into its slot of the result ring by the substitution itself -
  * no padded copy of C, no unpad launch.  211 or 100: the parts go together.  The results do not depend on it, bit for bit;
  * environment variable KP_SOLVE_BATCH_FORM=0 (read once) keeps the launch sequence of code 100 everywhere for A/B runs and tests.
- * 19: the kernel of the most recent batch of closed loops (koopman_hip_sim.h), ms. */
+ * 19: the kernel of the most recent batch of closed loops (koopman_hip_sim.h), ms.  20: not a time - the order in which the lift of
+ * the most recent Kronecker Gram launch dealt its (item, snapshot pair) jobs over the lift slots: 1 the dictionary's slot table
+ * (csrc/kp_gram3_lift.h: every job of three real factors in lift step 0, so that steps 1 and 2 read two table entries and multiply
+ * once), 0 the order slot = job (a dictionary with more than 256 such jobs, the forms without the in-kernel monomial lift, the
+ * KP_GRAM3_NOTUP form).  The results do not depend on it, bit for bit; environment variable KP_GRAM3_LIFT_ORDER=0 (read once) keeps
+ * order 0 everywhere for A/B runs and tests. */
 int kp_timer_get(const kp_ctx* ctx, int which, double* ms);
 /* Device pointer + byte size of the library stream's raw handle, for profilers/benchmarks
  * that want to bracket work with their own HIP events: returns hipStream_t as void*. */

@@ -36,10 +36,12 @@
 // scattered stores cost more), B operands 2 / 4 steps ahead and the raw load behind other steps (no difference), cbsz / abid
 // (they do not broadcast blocks on v_mfma_f64_4x4x4_4b: tools/mfma_bcast_probe.hip).
 // Later, on the one-A-group plan: a dictionary without fourth powers runs a form whose in-loop table build writes
-// three entries, not four (P3: 0.3068 -> 0.3044 ms per fit, kept).  Measured and NOT kept: the lift's jobs in an order built on
+// three entries, not four (P3: 0.3068 -> 0.3044 ms per fit, kept).  Measured and NOT kept THEN: the lift's jobs in an order built on
 // the host, every job of three real factors in lift step 0, so that steps 1 and 2 read two factors and multiply once - 4 v_mul_f64
 // and 2 ds_read_b128 less per wave and tile, but the compiler then reloads 5 spilled address registers inside every tile (none
-// before), behind the tile's raw load in the vmcnt order: 0.3068 -> 0.3127 ms.
+// before), behind the tile's raw load in the vmcnt order: 0.3068 -> 0.3127 ms.  Kept since DESIGN 6.7 (LO below): with the lift's
+// LDS byte addresses formed once and passed through an empty asm at the top of the tile body no tile loop holds a scratch
+// access and the loop is 5.5 vector instructions per wave and tile shorter: 0.2884 -> 0.2844 ms of kernel per fit.
 //
 // Replaces the per-row lift loop of Ksysid.get_Koopman (Ksysid.m:1030-1065) and the products
 // PxTPx, PxTPy (Ksysid.m:1114,1125) for model_type 'bilinear'.
@@ -85,6 +87,7 @@
 
 #include "kp_gram3_args.h"
 #include "kp_gram3_cover.h"
+#include "kp_gram3_lift.h"
 
 // the constant row of the in-loop power table "loads" its 1.0 like the raw rows load their values (kp_gram3_kernel, INL); not
 // `const`: a pointer that may be this or a kernel argument must stay a GLOBAL pointer (constant address space: flat loads)
@@ -99,10 +102,14 @@ __device__ double kp_gram3_ones[KT3] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
 // operand read per quad.  The weights sit in the 12 weight entries of a Psi row in tuple order (wslot), w_0 = 1 stored.
 // P3 (the in-kernel-lift monomial form without a projection; dictionaries of powers <= 3): the in-loop table build writes x, x^2, x^3 and no
 // x^4 entry that nothing reads - a v_mul_f64 and a ds_write_b64 less per wave and tile.
-template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool TUP = false, bool P3 = false>
+// LO (the same form, its default weight form; kp_gram3_lift.h): the lift's jobs sit in the slots of a table built on the host - every job of three
+// real factors in lift step 0, real factors first - so that lift steps 1 and 2 read two table entries and multiply once: 4
+// v_mul_f64 and 2 ds_read_b128 less per wave and tile, the same bits (a dropped factor is exactly 1.0).
+template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool TUP = false, bool P3 = false, bool LO = false>
 __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
   constexpr int NWT = (BM + 1) * (BM + 2) / 2;
   static_assert(!P3 || (!PCS && !EXT && !PRE), "three-entry table: the in-kernel-lift monomial form");
+  static_assert(!LO || (!PCS && !EXT && !PRE), "ordered lift slots: the in-kernel-lift monomial form");
   static_assert(!TUP || NWT % 2 == 0, "paired weights: an even number of weights (m = 3: 10 = 5 tuples, m = 2: 6 = 3 tuples)");
   // TUP: weight w sits in slot 6 (w & 1) + (w >> 1) of the 12 weight entries of a Psi row (w_0 = 1 stored in slot 0): the five
   // weights a lane multiplies in - w_{2p+h}, p = 0..4, h = blk >> 1 - are contiguous and 16-byte aligned (two ds_read_b128 and a
@@ -215,16 +222,39 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
     const int nitems = 2 * b.nfull + NWT - 1;
 #pragma unroll
     for (int j = 0; j < NLS; ++j) {
-      const int e = tid + 256 * j;
-      const bool on = e < 4 * nitems;
-      const int ch = on ? e / nitems : 0;
-      item_setup(on ? e - ch * nitems : -1, fs[j], ws[j]);
+      if constexpr (LO) {
+        // slot word (kp_gram3_lift.h): item | pair << 8 | three 2-bit factor sources from bit 10 (3: the constant)
+        const uint32_t sw = a.lift[tid + 256 * j];
+        const bool on = sw != GRAM3_LIFT_IDLE;
+        const int ch = on ? (int)((sw >> 8) & 3u) : 0;
+        int fr[NF3];
+        item_setup(on ? (int)(sw & 255u) : -1, fr, ws[j]);
 #pragma unroll
-      for (int f = 0; f < NF3; ++f) fs[j][f] += 2 * ch;
-      ws[j] += 2 * ch * RS3;
+        for (int f = 0; f < NF3; ++f) {
+          const int p = on ? (int)((sw >> (10 + 2 * f)) & 3u) : 3;
+          fs[j][f] = (p == 0 ? fr[0] : p == 1 ? fr[1] : p == 2 ? fr[2] : CA) + 2 * ch;
+        }
+        ws[j] += 2 * ch * RS3;
+      } else {
+        const int e = tid + 256 * j;
+        const bool on = e < 4 * nitems;
+        const int ch = on ? e / nitems : 0;
+        item_setup(on ? e - ch * nitems : -1, fs[j], ws[j]);
+#pragma unroll
+        for (int f = 0; f < NF3; ++f) fs[j][f] += 2 * ch;
+        ws[j] += 2 * ch * RS3;
+      }
     }
   }
 
+  // LO: the lift's LDS BYTE addresses, formed once (what the tile body pins: see there)
+  uint32_t fsb[NLS][NF3], wsb[NLS];
+#pragma unroll
+  for (int j = 0; j < NLS; ++j) {
+#pragma unroll
+    for (int f = 0; f < NF3; ++f) fsb[j][f] = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) double*)(sm + fs[j][f]);
+    wsb[j] = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) double*)(sm + ws[j]);
+  }
   const int64_t kt0 = (int64_t)split_local * a.ktiles_per_split;
   const int64_t ktiles_total = (a.Ns + KT3 - 1) / KT3;
   const int nkt = (int)max((int64_t)0, min((int64_t)a.ktiles_per_split, ktiles_total - kt0));
@@ -442,16 +472,34 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
   // ---- lift of a snapshot tile: power-table buffer B -> Psi buffer B, in pipelined chunks ----
   constexpr int NCH = NLS;                           // lift steps per tile
   double2 lf[NF3];
+  typedef double lds_d2 __attribute__((ext_vector_type(2)));   // (a 16-byte LDS read through an address-space pointer: no class type there)
+  auto lift_nf = [](int j) { return LO && j > 0 ? 2 : NF3; };   // factors a job of lift step j multiplies
   auto lift_read = [&](int j, auto buf_c) __attribute__((always_inline)) {
     constexpr int BUF = decltype(buf_c)::value;
 #pragma unroll
     for (int f = 0; f < NF3; ++f)      // (RB, PST3, CA and the pair offset are even: 16-byte aligned, one ds_read_b128)
-      lf[f] = *reinterpret_cast<const double2*>(__builtin_assume_aligned(&sm[BUF * POWBUF3 + fs[j][f]], 16));
+      if (f < lift_nf(j)) {
+        if constexpr (LO) {
+          const lds_d2 v = *(const __attribute__((address_space(3))) lds_d2*)(uintptr_t)(fsb[j][f] + (uint32_t)(BUF * POWBUF3 * 8));
+          lf[f].x = v.x;
+          lf[f].y = v.y;
+        } else lf[f] = *reinterpret_cast<const double2*>(__builtin_assume_aligned(&sm[BUF * POWBUF3 + fs[j][f]], 16));
+      }
   };
   auto lift_write = [&](int j, auto buf_c) __attribute__((always_inline)) {
     constexpr int BUF = decltype(buf_c)::value;
-    sm[BUF * PSIBUF3 + ws[j]] = (lf[0].x * lf[1].x) * lf[2].x;
-    sm[BUF * PSIBUF3 + ws[j] + RS3] = (lf[0].y * lf[1].y) * lf[2].y;
+    if constexpr (LO) {
+      const double px = lift_nf(j) == 2 ? lf[0].x * lf[1].x : (lf[0].x * lf[1].x) * lf[2].x;
+      const double py = lift_nf(j) == 2 ? lf[0].y * lf[1].y : (lf[0].y * lf[1].y) * lf[2].y;
+      *(__attribute__((address_space(3))) double*)(uintptr_t)(wsb[j] + (uint32_t)(BUF * PSIBUF3 * 8)) = px;
+      *(__attribute__((address_space(3))) double*)(uintptr_t)(wsb[j] + (uint32_t)((BUF * PSIBUF3 + RS3) * 8)) = py;
+    } else if (lift_nf(j) == 2) {
+      sm[BUF * PSIBUF3 + ws[j]] = lf[0].x * lf[1].x;
+      sm[BUF * PSIBUF3 + ws[j] + RS3] = lf[0].y * lf[1].y;
+    } else {
+      sm[BUF * PSIBUF3 + ws[j]] = (lf[0].x * lf[1].x) * lf[2].x;
+      sm[BUF * PSIBUF3 + ws[j] + RS3] = (lf[0].y * lf[1].y) * lf[2].y;
+    }
   };
   // Workgroup barrier behind LDS stores.  The table stores of store_tb_v are inline-assembly ds_write_b64: the compiler's
   // waitcnt insertion does not count them, so a bare __syncthreads() would not wait for them.  Every barrier that publishes
@@ -549,7 +597,7 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
   constexpr int NSTEP = (KT3 / 4) * NQ;                 // quad steps (NWT MFMAs each) per snapshot tile
   constexpr int SP = NSTEP / NCH > 0 ? NSTEP / NCH : 1;
   constexpr int LAG = SP / 2 > 0 ? SP / 2 : 1;
-  constexpr int PF_AHEAD = 3;                           // (2 and 4 steps ahead measured the same)
+  constexpr int PF_AHEAD = LO ? 2 : 3;                  // (2 and 4 steps ahead measured the same; LO: four registers for the lift's addresses)
   constexpr int PF = NSTEP < PF_AHEAD ? NSTEP : PF_AHEAD;   // B operands requested this many quad steps ahead
 
   // one snapshot tile: MFMAs on Psi buffer CUR, lift of the next tile into buffer 1-CUR, raw prefetch two ahead.
@@ -564,6 +612,20 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
     // load too (vmcnt counts in order) - with the load up here every wave sat out its HBM latency at the start of every tile.
     RawRegs rawreg;
     PreRegs prereg;
+    // LO: the lift's address registers pass through an empty asm at the top of every tile body.  Without it the allocator,
+    // two addresses lighter, spills one of them and reloads it inside every other tile body - behind the tile's raw load in the
+    // vmcnt order (the register table of every arrangement tried); with it no tile loop holds a scratch access.
+    // The BYTE addresses, not the offsets in doubles: behind the asm the value is opaque, and from a pinned offset the compiler
+    // re-formed base + 8 offset for all ten in every tile body (ten v_lshl_add_u32: measured, 1.9 % slower than the old order).
+    if constexpr (LO) {
+#pragma unroll
+      for (int j = 0; j < NLS; ++j) {
+#pragma unroll
+        for (int f = 0; f < NF3; ++f)
+          if (f < lift_nf(j)) asm volatile("" : "+v"(fsb[j][f]));
+        asm volatile("" : "+v"(wsb[j]));
+      }
+    }
     constexpr int NAW = TUP ? NWT / 2 : NWT;           // weighted A operands per A group (TUP: tuples of two weights)
     double bvs[NSTEP];
     double bvs2[TUP ? NSTEP : 1];                      // TUP: the quad's second B operand (groups 2, 3)
@@ -786,6 +848,10 @@ struct kp_gram3_plan {
   // the circulant plan of a dictionary owns its cover plan, built on first use (gram3_cover_plan); nullptr: none is kept
   kp_gram3_plan* cover = nullptr;
   bool cover_tried = false;
+  // ... and the dictionary's lift slot table (kp_gram3_lift.h), device, built on first use; nullptr behind lift_tried: the
+  // dictionary keeps the order e = tid + 256 j
+  uint32_t* lift = nullptr;
+  bool lift_tried = false;
 };
 
 void kp_gram3_plan_free(kp_gram3_plan* p) {
@@ -794,6 +860,7 @@ void kp_gram3_plan_free(kp_gram3_plan* p) {
   if (p->desc) (void)hipFree(p->desc);
   if (p->dst_off) (void)hipFree(p->dst_off);
   if (p->dst) (void)hipFree(p->dst);
+  if (p->lift) (void)hipFree(p->lift);
   delete p;
 }
 
@@ -836,21 +903,24 @@ static bool gram3_tup(int bm) {
   return bm >= 2 && !off;              // (an even number of weights: m = 2 -> 6, m = 3 -> 10)
 }
 
-template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool TUP = false, bool P3 = false>
+template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool TUP = false, bool P3 = false, bool LO = false>
 static hipError_t launch3c(const Gram3Args& a, int grid, size_t lds, hipStream_t st) {
   static KpLdsCache lds_cache;
   {
     const size_t lds_max = (size_t)(LDS3_DOUBLES + (PCS ? LDS3_PCS_DOUBLES : 0) + (EXT ? LDS3_GAUSS_DOUBLES : 0)) * sizeof(double);
-    hipError_t e = kp_ensure_lds(lds_cache, (const void*)kp_gram3_kernel<NQ, BM, PCS, EXT, PRE, TUP, P3>, lds_max);
+    hipError_t e = kp_ensure_lds(lds_cache, (const void*)kp_gram3_kernel<NQ, BM, PCS, EXT, PRE, TUP, P3, LO>, lds_max);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((kp_gram3_kernel<NQ, BM, PCS, EXT, PRE, TUP, P3>), dim3(grid), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((kp_gram3_kernel<NQ, BM, PCS, EXT, PRE, TUP, P3, LO>), dim3(grid), dim3(256), lds, st, a);
   return hipGetLastError();
 }
 
 template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false>
 static hipError_t launch3b(const Gram3Args& a, int grid, size_t lds, hipStream_t st) {
   if constexpr (!PCS && !EXT && !PRE) {
+    // the lift's jobs in the slots of the dictionary's table, in the default weight form (gram3_launch_n sets lift only there)
+    if (a.lift) return a.pow3 ? launch3c<NQ, BM, false, false, false, (BM >= 2), true, true>(a, grid, lds, st)
+                              : launch3c<NQ, BM, false, false, false, (BM >= 2), false, true>(a, grid, lds, st);
     // no fourth power in the dictionary: the three-entry table, in the default weight form (gram3_launch_n sets pow3 only there)
     if (a.pow3) return launch3c<NQ, BM, false, false, false, (BM >= 2), true>(a, grid, lds, st);
   }
@@ -1011,6 +1081,34 @@ static bool gram3_pow3_on() {
   return on;
 }
 
+// KP_GRAM3_LIFT_ORDER=0 (read once): the lift keeps the order e = tid + 256 j for every dictionary (A/B runs, tests)
+static bool gram3_lift_order_on() {
+  static const bool on = [] { const char* e = getenv("KP_GRAM3_LIFT_ORDER"); return !e || atoi(e) != 0; }();
+  return on;
+}
+
+// The dictionary's lift slot table (kp_gram3_lift.h), built and uploaded on first use and kept with its circulant plan;
+// *out = nullptr: the dictionary keeps today's order (more jobs of three real factors than lift step 0 has slots).
+static int gram3_lift_table(kp_ctx* ctx, kp_basis* basis, const uint32_t** out) {
+  kp_gram3_plan& circ = *basis->plan3;
+  *out = nullptr;
+  if (!circ.lift_tried) {
+    const BasisDev& b = basis->dev;
+    Gram3LiftOrderHost lo;
+    if (basis->fast && (int)basis->h_recipes.size() == b.nfull && gram3_lift_order_build(basis->h_recipes.data(), b.nfull, b.m, &lo)) {
+      hipError_t e = plan3_upload(&circ.lift, lo.slot);
+      if (e != hipSuccess) {
+        if (circ.lift) (void)hipFree(circ.lift);
+        circ.lift = nullptr;
+        return ctx->fail(KP_ERR_HIP, std::string("kp_fit_gram: lift table upload: ") + hipGetErrorString(e));
+      }
+    }
+    circ.lift_tried = true;
+  }
+  *out = circ.lift;
+  return KP_OK;
+}
+
 // the plan a launch runs: the dictionary's circulant plan, or its cover plan where the caller's path takes one and one is kept
 static int gram3_plan_for(kp_ctx* ctx, kp_basis* basis, bool deferred, kp_gram3_plan** out) {
   int rc = gram3_plan(ctx, basis);
@@ -1155,6 +1253,11 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   for (int f = 0; f < n; ++f) a.grp[f] = Gram3Src{ss[f]->alpha, ss[f]->beta, ss[f]->u};
   // the in-kernel-lift monomial form without a projection, in its default weight form: three table entries where no recipe reads a fourth
   a.pow3 = !pre && b.k_pcs == 0 && !ext && plan.wpw == 4 && basis->pow_depth <= 3 && (BM < 2 || gram3_tup(BM)) && gram3_pow3_on();
+  // ... and, in the same form, the lift's jobs in the slots of the dictionary's table (LO) where it has one
+  if (!pre && b.k_pcs == 0 && !ext && plan.wpw == 4 && (BM < 2 || gram3_tup(BM)) && gram3_lift_order_on()) {
+    int rc = gram3_lift_table(ctx, basis, &a.lift);
+    if (rc) return rc;
+  }
   const int grid = plan.nsuper * nsplit * n;
   // every event record is a barrier packet the command processor works through between two Gram kernels: the
   // pipelined path (ring_timing) keeps two (kernel start / end)
@@ -1212,6 +1315,8 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   ctx->timers[10] = (double)plan.njobs * plan.nq * NWT * 128.0 + (b.k_pcs > 0 && !pre ? (double)plan.nsuper * nfull4 * 128.0 : 0.0);
   // table entries per raw value that the in-loop build of this launch's kernel writes (0: a form without that build)
   ctx->timers[16] = (pre || ext || plan.wpw == 8) ? 0.0 : a.pow3 ? 3.0 : 4.0;
+  // the lift order this launch ran: 1 the dictionary's slot table, 0 the order e = tid + 256 j (a form without the in-kernel monomial lift too)
+  ctx->timers[20] = a.lift ? 1.0 : 0.0;
   ctx->timers[15] = (double)plan.two_group_jobs;   // jobs of this launch's plan that span two A groups (0: a one-A-group plan)
   return KP_OK;
 }

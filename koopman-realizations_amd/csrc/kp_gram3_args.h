@@ -36,6 +36,9 @@ struct Gram3Args {
   Gram3Src grp[KP_GRAM_GROUP_MAX] = {};
   // launcher only: the in-kernel-lift monomial form of a dictionary without fourth powers runs its three-entry table (P3)
   bool pow3 = false;
+  // the same form: its lift slot table (kp_gram3_lift.h: GRAM3_LIFT_SLOTS words) where the launch runs the ordered lift (LO),
+  // nullptr where it runs the order e = tid + 256 j
+  const uint32_t* lift = nullptr;
 };
 
 // one job per wave: kp_gram6_kernel<NQ, G4C> (kp_gram6.hip); hipErrorInvalidValue when no instantiation serves (nq, G4)
