@@ -100,7 +100,8 @@ int kp_device_info(const kp_ctx* ctx, char* name, int name_len, int* num_cu, int
  * (csrc/kp_gram3_lift.h: every job of three real factors in lift step 0, so that steps 1 and 2 read two table entries and multiply
  * once), 0 the order slot = job (a dictionary with more than 256 such jobs, the forms without the in-kernel monomial lift, the
  * KP_GRAM3_NOTUP form).  The results do not depend on it, bit for bit; environment variable KP_GRAM3_LIFT_ORDER=0 (read once) keeps
- * order 0 everywhere for A/B runs and tests. */
+ * order 0 everywhere for A/B runs and tests.  21: the kernel of the most recent batch of nonlinear closed loops (kp_nmpc_simulate,
+ * koopman_hip_nmpc.h), ms. */
 int kp_timer_get(const kp_ctx* ctx, int which, double* ms);
 /* Device pointer + byte size of the library stream's raw handle, for profilers/benchmarks
  * that want to bracket work with their own HIP events: returns hipStream_t as void*. */

@@ -35,6 +35,21 @@ typedef struct kp_nmpc kp_nmpc;           /* nonlinear MPC (SQP) problem on devi
  *   (iteration cap or no decrease along the step: the last iterate).
  * kp_nmpc_step_batch: nb independent problems of the same controller, every array per problem contiguous; the same
  *   kernel as kp_nmpc_step (its nb = 1 case).
+ * kp_nmpc_simulate: nb closed loops with the model itself as the plant (Kmpc.run_simulation, Kmpc.m:403-512) in one launch,
+ *   one workgroup per trial, everything in scaled units.  ref: [nb][nref][nproj] row-major, or one block for all trials
+ *   with ref_shared != 0; y0 [nb][nzeta], u0 [nb][m].  Step k = 1 .. nref-1 of a trial is the SQP of kp_nmpc_step (the
+ *   controller's options; mu and the damping restart at every step) at zeta = Y[k-1], u_prev = U[k-1] against reference rows
+ *   k-1 .. k-1+Np (the last row repeated behind the end); then U[k] = row 2 of its solution and Y[k] = F(Y[k-1], U[k-1]), the
+ *   one-step input delay of :495-496.  The start of a step is X0 (u_prev repeated); with warm != 0 and k > 1 the previous
+ *   step's returned inputs shifted by one row, last row repeated, row 1 = u_prev.  U [nb][nref][m], Y [nb][nref][nzeta], row 0
+ *   = u0 / y0; info ([nb][nref-1][3], may be NULL): SQP iterations, KKT residual, status of every step.  A step that ends
+ *   KP_ERR_NOT_CONVERGED returns its last iterate and the trial goes on; a failed QP subproblem ends that trial only:
+ *   steps_done[i] = k-1, rows k.. of U and Y and the info rows from that step on are NaN.  status[i]: KP_ERR_QP_FAIL (ended
+ *   early), KP_ERR_NOT_CONVERGED (completed with at least one unconverged step), else KP_OK; the call returns KP_OK whatever
+ *   the trials did.  nref = 1 writes row 0 and runs no step.  State bounds (kp_nmpc_set_state_bounds) hold in the loop.  A
+ *   trial's result does not depend on nb or on its index, bit for bit.  KP_ERR_ARG: nb < 1, nref < 1, a NULL pointer other
+ *   than info, horizon < 2, or the step's workspace plus the staged reference ((nref + Np) nproj doubles) beyond the 160 KB
+ *   of LDS.  kp_timer_get(21): the kernel, ms.
  * kp_nmpc_last_jacobians: [A_k B_k] = dF/d[zeta; u] at the Np points of the last linearisation of the last single step
  *   (Np blocks of nzeta x nvars, column-major). */
 int kp_lift_jacobian(kp_ctx* ctx, const kp_basis* basis, int nrows, const double* V, double* J);
@@ -48,6 +63,8 @@ int kp_nmpc_step(kp_nmpc* nmpc, const double* zeta, const double* u_prev, const 
                  double* U_out, double* Z_out, double* info, int* status);
 int kp_nmpc_step_batch(kp_nmpc* nmpc, int nb, const double* zeta, const double* u_prev, const double* Yr,
                        const double* U_init, double* U_out, double* Z_out, double* info, int* status);
+int kp_nmpc_simulate(kp_nmpc* nmpc, int nb, int nref, const double* ref, int ref_shared, const double* y0, const double* u0,
+                     int warm, double* U, double* Y, double* info, int* steps_done, int* status);
 int kp_nmpc_last_jacobians(kp_nmpc* nmpc, double* J);
 int kp_nmpc_destroy(kp_nmpc* nmpc);
 

@@ -133,9 +133,11 @@ NMPC_SIGNATURES = {
     "kp_nmpc_dims": (C.c_int, [vp, c_ip, c_ip]),
     "kp_nmpc_step": (C.c_int, [vp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_ip]),
     "kp_nmpc_step_batch": (C.c_int, [vp, C.c_int, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_ip]),
+    "kp_nmpc_simulate": (C.c_int, [vp, C.c_int, C.c_int, c_dp, C.c_int, c_dp, c_dp, C.c_int, c_dp, c_dp, c_dp, c_ip, c_ip]),
     "kp_nmpc_last_jacobians": (C.c_int, [vp, c_dp]),
     "kp_nmpc_destroy": (C.c_int, [vp]),
 }
+TIMER_NMPC_SIM = 21                # kp_timer_get slot: the kernel of the most recent kp_nmpc_simulate, ms
 
 # the batched load observer (include/koopman_hip_observer.h)
 OBSERVER_SIGNATURES = {

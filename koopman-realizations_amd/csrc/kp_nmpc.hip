@@ -284,13 +284,36 @@ __device__ __forceinline__ void nm_block2(double& a, double& b, double* red, boo
   __syncthreads();
 }
 
-__global__ __launch_bounds__(256) void kp_nmpc_kernel(NmpcArgs a) {
-  extern __shared__ __align__(16) double sm[];
-  const int tid = threadIdx.x, pb = blockIdx.x;
+// The dense constraint matrix of a controller with state bounds (global memory, [mr x nU] per problem): its linear rows.
+// They are constant; the state rows behind them are rewritten at every linearisation.
+__device__ __forceinline__ void nmpc_dense_lin_rows(const NmpcArgs& a, double* dval, double* dnorm) {
+  const int nlin = a.nlin, nU = a.nU, mr = a.mr;
+  for (int row = threadIdx.x; row < nlin; row += 256) {
+    for (int k = 0; k < nU; ++k) dval[(size_t)k * mr + row] = 0.0;
+    for (int k = 0; k < a.lin.K; ++k) {
+      const double v = a.lin.val[k * nlin + row];
+      if (v != 0.0) dval[(size_t)a.lin.col[k * nlin + row] * mr + row] = v;
+    }
+    dnorm[row] = a.lin.norm[row];
+  }
+}
+
+// One SQP step of problem pb; returns its status, the iteration count and the KKT residual, and leaves the returned inputs in
+// the U block and their rollout z_0 .. z_Np in the Z block of LDS.
+// SIM = false (kp_nmpc_kernel): the problem's inputs come from a.in, Kfull and the dense linear rows are staged here, the
+//   results go to a.out / a.status.
+// SIM = true (kp_nmpc_sim_kernel): Kfull, zeta0, up and the dense linear rows are in place, the reference window is yr_sim
+//   (LDS), and the start is X0 (up repeated) or, with warm, the U block's previous content shifted by one row, last row
+//   repeated, row 1 = up.  Nothing is written to global memory but the state rows of the dense matrix.
+template <bool SIM>
+__device__ __forceinline__ int nmpc_step_body(const NmpcArgs& a, double* sm, const int pb, const double* yr_sim, const bool warm,
+                                              int& it_out, double& kkt_out) {
+  const int tid = threadIdx.x;
   const NmpcLayout& L = a.L;
   const BasisDev& b = a.b;
   const int nz = a.nz, m = a.m, nv = a.nv, Np = a.Np, nproj = a.nproj, nU = a.nU, mr = a.mr, nlin = a.nlin, nfull = b.nfull;
-  double *Kfull = sm + L.Kfull, *zeta0 = sm + L.zeta0, *up = sm + L.up, *Yr = sm + L.Yr, *U = sm + L.U, *dU = sm + L.dU,
+  const double* Yr = SIM ? yr_sim : sm + L.Yr;
+  double *Kfull = sm + L.Kfull, *zeta0 = sm + L.zeta0, *up = sm + L.up, *U = sm + L.U, *dU = sm + L.dU,
          *Ut = sm + L.Ut, *V = sm + L.V, *Vt = sm + L.Vt, *Z = sm + L.Z, *Zt = sm + L.Zt, *full = sm + L.full,
          *dfull = sm + L.dfull, *Jac = sm + L.Jac, *S = sm + L.S, *P = sm + L.P, *ev = sm + L.ev, *f = sm + L.f,
          *Hq = sm + L.Hq, *bq = sm + L.bq, *red = sm + L.red, *sc = sm + L.sc, *qws = sm + L.qws;
@@ -302,29 +325,32 @@ __global__ __launch_bounds__(256) void kp_nmpc_kernel(NmpcArgs a) {
   const double* sb_hi = a.sb_lohi + nz;
   const int tack0 = nlin - 2 * m;
 
-  for (int e = tid; e < nz * nfull; e += 256) Kfull[e] = a.Kfull[e];
-  for (int e = tid; e < nz; e += 256) zeta0[e] = in[e];
-  for (int e = tid; e < m; e += 256) up[e] = in[nz + e];
-  for (int e = tid; e < (Np + 1) * nproj; e += 256) Yr[e] = in[nz + m + e];
-  const int o_init = nz + m + (Np + 1) * nproj;
-  const bool has_init = in[o_init] != 0.0;
-  __syncthreads();
-  for (int j = tid; j < nU; j += 256) U[j] = j < m ? up[j] : (has_init ? in[o_init + 1 + j] : up[j % m]);   // u_1 = u_prev (:1152, X0 :1155)
+  if constexpr (!SIM) {
+    double* Yrs = sm + L.Yr;
+    for (int e = tid; e < nz * nfull; e += 256) Kfull[e] = a.Kfull[e];
+    for (int e = tid; e < nz; e += 256) zeta0[e] = in[e];
+    for (int e = tid; e < m; e += 256) up[e] = in[nz + e];
+    for (int e = tid; e < (Np + 1) * nproj; e += 256) Yrs[e] = in[nz + m + e];
+    const int o_init = nz + m + (Np + 1) * nproj;
+    const bool has_init = in[o_init] != 0.0;
+    __syncthreads();
+    for (int j = tid; j < nU; j += 256) U[j] = j < m ? up[j] : (has_init ? in[o_init + 1 + j] : up[j % m]);   // u_1 = u_prev (:1152, X0 :1155)
+  } else {
+    double u_start = 0.0;                       // (nU <= 64: one entry per thread)
+    if (tid < nU) {
+      const int row = tid / m, i = tid - row * m;
+      u_start = row == 0 ? up[i] : (warm ? U[min(row + 1, Np - 1) * m + i] : up[i]);
+    }
+    __syncthreads();                            // (every read of the previous solution is done)
+    if (tid < nU) U[tid] = u_start;
+  }
   // right-hand side of linear row `row` (the tack rows pin u_1 to u_prev)
   auto lin_rhs = [&](int row) -> double {
     const int t = row - tack0;
     return t < 0 ? a.lin_b[row] : (t < m ? up[t] : -up[t - m]);
   };
-  if (a.sb) {   // the linear rows of the dense constraint matrix, once per step
-    for (int row = tid; row < nlin; row += 256) {
-      for (int k = 0; k < nU; ++k) dval[(size_t)k * mr + row] = 0.0;
-      for (int k = 0; k < a.lin.K; ++k) {
-        const double v = a.lin.val[k * nlin + row];
-        if (v != 0.0) dval[(size_t)a.lin.col[k * nlin + row] * mr + row] = v;
-      }
-      dnorm[row] = a.lin.norm[row];
-    }
-  }
+  if constexpr (!SIM)
+    if (a.sb) nmpc_dense_lin_rows(a, dval, dnorm);   // the linear rows of the dense constraint matrix, once per step
   __syncthreads();
 
   // ---- rollout of Ub: points Vb [k][nv] = [z_k; u_{k+1}], states Zb [k][nz]; returns (J, sum of constraint violations) ----
@@ -560,22 +586,123 @@ __global__ __launch_bounds__(256) void kp_nmpc_kernel(NmpcArgs a) {
     __syncthreads();
   }
 
-  double* out = a.out + (size_t)pb * a.out_per;
-  for (int j = tid; j < nU; j += 256) out[j] = status == KP_ERR_QP_FAIL ? __builtin_nan("") : U[j];
-  for (int e = tid; e < (Np + 1) * nz; e += 256) out[nU + e] = Z[e];
-  if (tid == 0) {
-    out[nU + (Np + 1) * nz] = (double)it;
-    out[nU + (Np + 1) * nz + 1] = kkt;
-    a.status[pb] = status;
-  }
-  if (a.jac_out && pb == 0)
-    for (int e = tid; e < Np * nz * nv; e += 256) a.jac_out[e] = Jac[e];
-  if (a.done_flag && pb == 0) {
-    __syncthreads();
+  it_out = it;
+  kkt_out = kkt;
+  if constexpr (!SIM) {
+    double* out = a.out + (size_t)pb * a.out_per;
+    for (int j = tid; j < nU; j += 256) out[j] = status == KP_ERR_QP_FAIL ? __builtin_nan("") : U[j];
+    for (int e = tid; e < (Np + 1) * nz; e += 256) out[nU + e] = Z[e];
     if (tid == 0) {
+      out[nU + (Np + 1) * nz] = (double)it;
+      out[nU + (Np + 1) * nz + 1] = kkt;
+      a.status[pb] = status;
+    }
+    if (a.jac_out && pb == 0)
+      for (int e = tid; e < Np * nz * nv; e += 256) a.jac_out[e] = Jac[e];
+  }
+  return status;
+}
+
+__global__ __launch_bounds__(256) void kp_nmpc_kernel(NmpcArgs a) {
+  extern __shared__ __align__(16) double sm[];
+  int it;
+  double kkt;
+  nmpc_step_body<false>(a, sm, blockIdx.x, nullptr, false, it, kkt);
+  if (a.done_flag && blockIdx.x == 0) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
       __threadfence_system();
       __hip_atomic_store(&a.done_flag[0], a.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+  }
+}
+
+// ---- whole closed loops with the model as the plant (kp_nmpc_simulate; Kmpc.run_simulation, Kmpc.m:403-512) -----------
+// One workgroup per trial runs steps k = 1 .. nref - 1 in scaled units: the SQP of kp_nmpc_step at zeta = Y[k-1],
+// u_prev = U[k-1] against rows k-1 .. k-1+Np of the reference (its last row repeated behind its end, :354-365), then
+// U[k] = the solution's second row and Y[k] = z_1 of the solution's rollout = F(zeta, u_prev), because u_1 is pinned to u_prev:
+// the one-step input delay of :495-496.  mu and the damping restart at every step, as in separate launches.
+// Staged once per trial: Kfull, the reference with Np trailing copies of its last row behind the step's block (at sim_off:
+// every step's window is one contiguous block) and, with state bounds, the constant linear rows of the trial's dense
+// constraint matrix.  zeta, u_prev and the previous solution U stay in the step's own LDS blocks from one step to the next;
+// U, Y and info rows are only ever written.  A failed QP subproblem ends the trial (the break of :483-485); an unconverged
+// step returns its last iterate and the trial goes on.  A trial touches nothing that depends on blockIdx.x except its own
+// rows, so its result does not depend on nb or on its index.  Every loop is bounded by nref, max_iter and NMPC_LS_MAX.
+struct NmpcSimArgs {
+  int nref, ref_shared, warm, sim_off;
+  const double *ref, *y0, *u0;      // [nb or 1][nref][nproj], [nb][nz], [nb][m]
+  double *U, *Y, *info;             // [nb][nref][m], [nb][nref][nz], [nb][nref - 1][3] or nullptr
+  int *steps_done, *status;         // [nb]
+};
+__global__ __launch_bounds__(256) void kp_nmpc_sim_kernel(NmpcArgs a, NmpcSimArgs sa) {
+  extern __shared__ __align__(16) double sm[];
+  const int tid = threadIdx.x, pb = blockIdx.x;
+  const size_t trial = blockIdx.x;
+  const NmpcLayout& L = a.L;
+  const int nz = a.nz, m = a.m, Np = a.Np, nproj = a.nproj, nref = sa.nref, nfull = a.b.nfull;
+  double *Kfull = sm + L.Kfull, *zeta0 = sm + L.zeta0, *up = sm + L.up, *U = sm + L.U, *Z = sm + L.Z, *refl = sm + sa.sim_off;
+  double* Ut = sa.U + trial * (size_t)nref * m;
+  double* Yt = sa.Y + trial * (size_t)nref * nz;
+  double* It = sa.info ? sa.info + trial * (size_t)(nref - 1) * 3 : nullptr;
+  // ---- once per trial ----
+  for (int e = tid; e < nz * nfull; e += 256) Kfull[e] = a.Kfull[e];
+  {
+    const double* rt = sa.ref + (sa.ref_shared ? 0 : trial * (size_t)nref * nproj);
+    for (int e = tid; e < (nref + Np) * nproj; e += 256) {
+      const int row = e / nproj, p = e - row * nproj;
+      refl[e] = rt[(size_t)min(row, nref - 1) * nproj + p];
+    }
+  }
+  for (int e = tid; e < nz; e += 256) {
+    const double v = sa.y0[trial * nz + e];
+    zeta0[e] = v;
+    Yt[e] = v;
+  }
+  for (int e = tid; e < m; e += 256) {
+    const double v = sa.u0[trial * m + e];
+    up[e] = v;
+    Ut[e] = v;
+  }
+  if (a.sb) nmpc_dense_lin_rows(a, a.dval + trial * (size_t)a.mr * a.nU, a.dnorm + trial * (size_t)a.mr);
+  __syncthreads();
+  const double qnan = __builtin_nan("");
+  int k = 1, failed = 0, unconverged = 0;
+  for (; k < nref; ++k) {
+    int it;
+    double kkt;
+    const int st = nmpc_step_body<true>(a, sm, pb, refl + (size_t)(k - 1) * nproj, sa.warm != 0 && k > 1, it, kkt);
+    if (st == KP_ERR_QP_FAIL) {             // (uniform)
+      failed = 1;
+      break;
+    }
+    unconverged |= st != KP_OK;
+    __syncthreads();                        // (every read of zeta0 and up is done; U and Z are the step's results)
+    for (int e = tid; e < nz; e += 256) {
+      const double v = Z[nz + e];           // z_1 = F(zeta, u_prev)
+      zeta0[e] = v;
+      Yt[(size_t)k * nz + e] = v;
+    }
+    for (int e = tid; e < m; e += 256) {
+      const double v = U[m + e];            // the second row of the solution
+      up[e] = v;
+      Ut[(size_t)k * m + e] = v;
+    }
+    if (It && tid == 0) {
+      It[(size_t)(k - 1) * 3] = (double)it;
+      It[(size_t)(k - 1) * 3 + 1] = kkt;
+      It[(size_t)(k - 1) * 3 + 2] = (double)st;
+    }
+    __syncthreads();
+  }
+  if (failed) {   // rows k .. nref-1 of U and Y and the info rows from this step's on: NaN
+    for (size_t e = (size_t)k * m + tid; e < (size_t)nref * m; e += 256) Ut[e] = qnan;
+    for (size_t e = (size_t)k * nz + tid; e < (size_t)nref * nz; e += 256) Yt[e] = qnan;
+    if (It)
+      for (size_t e = (size_t)(k - 1) * 3 + tid; e < (size_t)(nref - 1) * 3; e += 256) It[e] = qnan;
+  }
+  if (tid == 0) {
+    sa.steps_done[trial] = k - 1;
+    sa.status[trial] = failed ? KP_ERR_QP_FAIL : (unconverged ? KP_ERR_NOT_CONVERGED : KP_OK);
   }
 }
 
@@ -803,6 +930,30 @@ extern "C" int kp_nmpc_set_options(kp_nmpc* M, int max_iter, double tol_kkt, dou
   return KP_OK;
 }
 
+// State bounds: the dense constraint rows of every problem (or trial) of a launch.
+static int nmpc_ensure_dense(kp_nmpc* M, int nb) {
+  kp_ctx* ctx = M->ctx;
+  const int nU = M->nU, mr = nmpc_rows(M);
+  if (M->sb && M->dense_problems < (size_t)nb) {
+    if (M->dval) (void)hipFree(M->dval);
+    if (M->dnorm) (void)hipFree(M->dnorm);
+    if (M->dcol) (void)hipFree(M->dcol);
+    M->dval = M->dnorm = nullptr;
+    M->dcol = nullptr;
+    M->dense_problems = 0;
+    // (the column table is sized for the largest row count: with state bounds mr is fixed by the controller)
+    KP_HIP(ctx, hipMalloc((void**)&M->dval, (size_t)nb * mr * nU * 8));
+    KP_HIP(ctx, hipMalloc((void**)&M->dnorm, (size_t)nb * mr * 8));
+    KP_HIP(ctx, hipMalloc((void**)&M->dcol, (size_t)mr * nU * 4));
+    std::vector<int> col((size_t)mr * nU);
+    for (int k = 0; k < nU; ++k)
+      for (int row = 0; row < mr; ++row) col[(size_t)k * mr + row] = k;
+    KP_HIP(ctx, hipMemcpy(M->dcol, col.data(), col.size() * 4, hipMemcpyHostToDevice));
+    M->dense_problems = nb;
+  }
+  return KP_OK;
+}
+
 extern "C" int kp_nmpc_step_batch(kp_nmpc* M, int nb, const double* zeta, const double* u_prev, const double* Yr, const double* U_init,
                                   double* U_out, double* Z_out, double* info, int* status) {
   if (!M) return KP_ERR_ARG;
@@ -826,23 +977,7 @@ extern "C" int kp_nmpc_step_batch(kp_nmpc* M, int nb, const double* zeta, const 
     M->io_problems = nb;
   }
   M->h_status = (int*)(M->h_out + M->io_problems * out_per);
-  if (M->sb && M->dense_problems < (size_t)nb) {
-    if (M->dval) (void)hipFree(M->dval);
-    if (M->dnorm) (void)hipFree(M->dnorm);
-    if (M->dcol) (void)hipFree(M->dcol);
-    M->dval = M->dnorm = nullptr;
-    M->dcol = nullptr;
-    M->dense_problems = 0;
-    // (the column table is sized for the largest row count: with state bounds mr is fixed by the controller)
-    KP_HIP(ctx, hipMalloc((void**)&M->dval, (size_t)nb * mr * nU * 8));
-    KP_HIP(ctx, hipMalloc((void**)&M->dnorm, (size_t)nb * mr * 8));
-    KP_HIP(ctx, hipMalloc((void**)&M->dcol, (size_t)mr * nU * 4));
-    std::vector<int> col((size_t)mr * nU);
-    for (int k = 0; k < nU; ++k)
-      for (int row = 0; row < mr; ++row) col[(size_t)k * mr + row] = k;
-    KP_HIP(ctx, hipMemcpy(M->dcol, col.data(), col.size() * 4, hipMemcpyHostToDevice));
-    M->dense_problems = nb;
-  }
+  if (int rcd = nmpc_ensure_dense(M, nb)) return rcd;
   for (int p = 0; p < nb; ++p) {
     double* in = M->h_in + (size_t)p * in_per;
     memcpy(in, zeta + (size_t)p * nz, (size_t)nz * 8);
@@ -905,6 +1040,100 @@ extern "C" int kp_nmpc_step_batch(kp_nmpc* M, int nb, const double* zeta, const 
 extern "C" int kp_nmpc_step(kp_nmpc* M, const double* zeta, const double* u_prev, const double* Yr, const double* U_init,
                             double* U_out, double* Z_out, double* info, int* status) {
   return kp_nmpc_step_batch(M, 1, zeta, u_prev, Yr, U_init, U_out, Z_out, info, status);
+}
+
+// Whole closed loops, one workgroup per trial (kp_nmpc_sim_kernel).  Host transfers as kp_mpc_simulate: the inputs cross in
+// one packed copy; the outputs come back through the page-locked scratch in one copy up to 4 MB, else straight into the
+// caller's arrays.
+#define KP_NMPC_SIM_PINNED_BYTES ((size_t)4 << 20)
+extern "C" int kp_nmpc_simulate(kp_nmpc* M, int nb, int nref, const double* ref, int ref_shared, const double* y0, const double* u0,
+                                int warm, double* U, double* Y, double* info, int* steps_done, int* status) {
+  if (!M) return KP_ERR_ARG;
+  kp_ctx* ctx = M->ctx;
+  if (nb < 1 || nref < 1)
+    return ctx->fail(KP_ERR_ARG, "kp_nmpc_simulate: nb and nref must be at least 1 (nb = " + std::to_string(nb) + ", nref = " +
+                                     std::to_string(nref) + ")");
+  if (!ref || !y0 || !u0 || !U || !Y || !steps_done || !status)
+    return ctx->fail(KP_ERR_ARG, "kp_nmpc_simulate: NULL argument (only info may be NULL)");
+  const int nz = M->nz, m = M->m, Np = M->Np, nproj = M->nproj, nUv = M->nU, mr = nmpc_rows(M);
+  if (Np < 2) return ctx->fail(KP_ERR_ARG, "kp_nmpc_simulate: the loop applies the second row of the solution: horizon >= 2");
+  NmpcSimArgs sa{};
+  NmpcArgs a{};
+  a.L = nmpc_layout(nz, m, Np, nproj, M->basis->dev.nfull, mr);
+  sa.sim_off = a.L.total;
+  const size_t ref_doubles = (((size_t)nref + Np) * nproj + 1) & ~(size_t)1;
+  const size_t lds = ((size_t)a.L.total + ref_doubles) * 8;
+  if (lds > NMPC_LDS_MAX)
+    return ctx->fail(KP_ERR_ARG, "kp_nmpc_simulate: the step's workspace and a reference of " + std::to_string(nref) + " rows need " +
+                                     std::to_string(lds) + " bytes of LDS (" + std::to_string(NMPC_LDS_MAX) + " at most)");
+  KP_HIP(ctx, hipSetDevice(ctx->device));
+  if (ctx->async_pending) {
+    int rc0 = kp_synchronize(ctx);
+    if (rc0) return rc0;
+  }
+  if (int rcd = nmpc_ensure_dense(M, nb)) return rcd;
+  a.b = M->basis->dev;
+  a.nz = nz; a.m = m; a.nv = M->nv; a.Np = Np; a.nproj = nproj; a.nU = nUv; a.nlin = M->nlin; a.mr = mr; a.sb = M->sb;
+  a.max_iter = M->max_iter;
+  a.q_run = M->q_run; a.q_term = M->q_term; a.tol_kkt = M->tol_kkt; a.tol_step = M->tol_step;
+  a.damping = M->damping;
+  a.Kv = M->Kv; a.Kfull = M->Kfull; a.cvec = M->cvec; a.proj = M->proj; a.r = M->r; a.sb_lohi = M->sb_lohi;
+  a.lin = EllMat{M->lin_val, M->lin_col, M->lin_norm, M->linK};
+  a.lin_b = M->lin_b;
+  a.dval = M->dval; a.dcol = M->dcol; a.dnorm = M->dnorm;
+  // device block: [ref | y0 | u0] | U | Y | info | steps_done, status
+  const size_t nR = (size_t)(ref_shared ? 1 : nb) * nref * nproj, nY0 = (size_t)nb * nz, nU0 = (size_t)nb * m, n_in = nR + nY0 + nU0;
+  const size_t nU = (size_t)nb * nref * m, nY = (size_t)nb * nref * nz, nI = info ? (size_t)nb * (nref - 1) * 3 : 0;
+  const size_t n_int = ((size_t)2 * nb + 1) / 2, n_out = nU + nY + nI + n_int;
+  double* ws = (double*)ctx->workspace(6, (n_in + n_out) * 8);
+  if (!ws) return ctx->fail(KP_ERR_HIP, "kp_nmpc_simulate: out of device memory");
+  const bool pinned = (n_in + n_out) * 8 <= KP_NMPC_SIM_PINNED_BYTES;
+  std::vector<double> h_vec;
+  double* h = nullptr;
+  if (pinned) {
+    h = (double*)kp_pinned_scratch(ctx, (n_in + n_out) * 8);
+    if (!h) return ctx->fail(KP_ERR_HIP, "kp_nmpc_simulate: out of page-locked memory");
+  } else {
+    h_vec.resize(n_in);
+    h = h_vec.data();
+  }
+  memcpy(h, ref, nR * 8);
+  memcpy(h + nR, y0, nY0 * 8);
+  memcpy(h + nR + nY0, u0, nU0 * 8);
+  hipStream_t s = ctx->stream;
+  KP_HIP(ctx, hipMemcpyAsync(ws, h, n_in * 8, hipMemcpyHostToDevice, s));
+  double* d_out = ws + n_in;
+  sa.nref = nref; sa.ref_shared = ref_shared ? 1 : 0; sa.warm = warm ? 1 : 0;
+  sa.ref = ws; sa.y0 = ws + nR; sa.u0 = ws + nR + nY0;
+  sa.U = d_out; sa.Y = d_out + nU; sa.info = nI ? d_out + nU + nY : nullptr;
+  sa.steps_done = (int*)(d_out + nU + nY + nI);
+  sa.status = sa.steps_done + nb;
+  static KpLdsCache sim_lds;
+  KP_HIP(ctx, kp_ensure_lds(sim_lds, (const void*)kp_nmpc_sim_kernel, lds));
+  KP_HIP(ctx, hipEventRecord(ctx->evp[4], s));
+  hipLaunchKernelGGL(kp_nmpc_sim_kernel, dim3(nb), dim3(256), lds, s, a, sa);
+  KP_HIP(ctx, hipGetLastError());
+  KP_HIP(ctx, hipEventRecord(ctx->evp[5], s));
+  if (pinned) {
+    double* h_out = h + n_in;
+    KP_HIP(ctx, hipMemcpyAsync(h_out, d_out, n_out * 8, hipMemcpyDeviceToHost, s));
+    KP_HIP(ctx, hipStreamSynchronize(s));
+    memcpy(U, h_out, nU * 8);
+    memcpy(Y, h_out + nU, nY * 8);
+    if (nI) memcpy(info, h_out + nU + nY, nI * 8);
+    memcpy(steps_done, h_out + nU + nY + nI, (size_t)nb * sizeof(int));
+    memcpy(status, (const int*)(h_out + nU + nY + nI) + nb, (size_t)nb * sizeof(int));
+  } else {
+    KP_HIP(ctx, hipMemcpyAsync(U, sa.U, nU * 8, hipMemcpyDeviceToHost, s));
+    KP_HIP(ctx, hipMemcpyAsync(Y, sa.Y, nY * 8, hipMemcpyDeviceToHost, s));
+    if (nI) KP_HIP(ctx, hipMemcpyAsync(info, sa.info, nI * 8, hipMemcpyDeviceToHost, s));
+    KP_HIP(ctx, hipMemcpyAsync(steps_done, sa.steps_done, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s));
+    KP_HIP(ctx, hipMemcpyAsync(status, sa.status, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s));
+    KP_HIP(ctx, hipStreamSynchronize(s));
+  }
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, ctx->evp[4], ctx->evp[5]) == hipSuccess) ctx->timers[21] = ms;
+  return KP_OK;
 }
 
 extern "C" int kp_nmpc_last_jacobians(kp_nmpc* M, double* J) {

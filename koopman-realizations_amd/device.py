@@ -963,6 +963,32 @@ class Nmpc:
                                            F.dptr(info), st.ctypes.data_as(F.c_ip)), self.ctx.handle)
         return np.transpose(U, (0, 2, 1)), Z, info, st
 
+    def simulate(self, ref_sc, y0_sc, u0_sc, warm=False, want_info=True):
+        """kp_nmpc_simulate: nb closed loops with the model as the plant in one launch (Kmpc.run_simulation's loop, scaled
+        units).  ref_sc: (nref, nproj) for every trial or (nb, nref, nproj); y0_sc (nb, nzeta), u0_sc (nb, m).  warm: every
+        step but the first starts from the previous step's solution, shifted.  Returns (U (nb, nref, m), Y (nb, nref, nzeta),
+        info (nb, nref-1, 3): SQP iterations, KKT residual, status of every step (None without want_info), steps_done (nb,),
+        status (nb,)); rows behind a failed step are NaN.  The kernel time is ctx.timer(F.TIMER_NMPC_SIM) afterwards, ms."""
+        y0 = np.ascontiguousarray(np.atleast_2d(y0_sc), dtype=np.float64)
+        u0 = np.ascontiguousarray(np.atleast_2d(u0_sc), dtype=np.float64)
+        ref = np.ascontiguousarray(ref_sc, dtype=np.float64)
+        nb = y0.shape[0]
+        shared = ref.ndim == 2
+        if ref.ndim not in (2, 3) or ref.shape[-1] != self.nproj or (not shared and ref.shape[0] != nb):
+            raise ValueError(f"ref_sc must be (nref, {self.nproj}) or ({nb}, nref, {self.nproj}), not {ref.shape}")
+        if y0.shape[1] != self.nzeta:
+            raise ValueError(f"y0_sc must be ({nb}, {self.nzeta}), not {y0.shape}")
+        if u0.shape != (nb, self.m):
+            raise ValueError(f"u0_sc must be ({nb}, {self.m}), not {u0.shape}")
+        nref = ref.shape[-2]
+        U = np.zeros((nb, nref, self.m)); Y = np.zeros((nb, nref, self.nzeta))
+        info = np.zeros((nb, max(nref - 1, 0), 3)) if want_info else None
+        sd = np.zeros(nb, dtype=np.int32); st = np.zeros(nb, dtype=np.int32)
+        F.check(F.lib().kp_nmpc_simulate(self._h, nb, nref, F.dptr(ref), 1 if shared else 0, F.dptr(y0), F.dptr(u0),
+                                         1 if warm else 0, F.dptr(U), F.dptr(Y), F.dptr(info), sd.ctypes.data_as(F.c_ip),
+                                         st.ctypes.data_as(F.c_ip)), self.ctx.handle)
+        return U, Y, info, sd, st
+
     def last_jacobians(self):
         """[A_k B_k] = dF/d[zeta; u] at the Np points of the last linearisation of the last single step: (Np, nzeta, nvars)."""
         nv = self.nzeta + self.m

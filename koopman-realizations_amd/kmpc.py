@@ -11,7 +11,8 @@ uses it when fused_load_step is true (the default) and the host-assembled estima
 state_bounds (Kmpc.m:300-318) are scaled down like the reference does and handed to kp_mpc_set_state_bounds.
 Nonlinear models (model_type 'nonlinear', mpc_type 'nonlinear'): get_mpcInput_nonlinear (Kmpc.m:1114-1181) solves the
 reference's fmincon SQP problem by a single-shooting SQP in one kernel launch (kp_nmpc_step), in the one configuration the
-reference runs: unloaded, nd = 0.  Out of scope: bilinear models with mpc_type 'nonlinear', the unused nlmpc glue.
+reference runs: unloaded, nd = 0; run_simulation is the host loop of such steps with the model as the plant,
+run_simulations runs every trial's whole loop in one launch (kp_nmpc_simulate).  Out of scope: bilinear models with mpc_type 'nonlinear', the unused nlmpc glue.
 """
 from __future__ import annotations
 
@@ -281,6 +282,8 @@ class Kmpc:
         u0 = np.zeros(m) if u0 is None else np.asarray(u0, dtype=np.float64)
         ref_sc = self.scaledown_ref(ref_y)
         res = {"T": [0.0], "U": [u0], "Y": [y0], "K": [0], "R": [np.atleast_2d(ref_y)[0]], "Z": [], "comp_time": []}
+        if self.model_type == "nonlinear":
+            return self._run_simulation_nonlinear(ref_sc, res)
         k = 1
         while k < ref_sc.shape[0]:
             cur = {"y": s.scaledown_y(res["Y"][-1])[None, :], "u": s.scaledown_u(res["U"][-1])[None, :]}
@@ -303,6 +306,31 @@ class Kmpc:
             k += 1
         return {k_: np.array(v) for k_, v in res.items()}
 
+    def _run_simulation_nonlinear(self, ref_sc, res):
+        """run_simulation's loop for a nonlinear model: one SQP launch per step (get_mpcInput_nonlinear), the plant step
+        F(zeta, u_{k-1}) on the host.  Adds nmpc_info: (SQP iterations, KKT residual, status) of every step, as Ksim does.
+        A warm start (nmpc_warm_start) begins anew with every run."""
+        p, s = self.params, self.sysid
+        self._U_last = None
+        res["nmpc_info"] = []
+        k = 1
+        while k < ref_sc.shape[0]:
+            cur = {"y": s.scaledown_y(res["Y"][-1])[None, :], "u": s.scaledown_u(res["U"][-1])[None, :]}
+            t0 = time.perf_counter()
+            U, z = self.get_mpcInput_nonlinear(cur, ref_sc[k - 1:k + self.horizon])
+            res["comp_time"].append(time.perf_counter() - t0)
+            res["nmpc_info"].append(self.last_info)
+            if np.isnan(U).any():
+                break
+            y1 = self.model["F_func"](cur["y"][0], cur["u"][0])          # Kmpc.m:495 one-step input delay
+            res["T"].append(k * p["Ts"]); res["U"].append(s.scaleup_u(U[1])); res["Y"].append(s.scaleup_y(y1))
+            res["K"].append(k); res["R"].append(self.scaleup_ref(ref_sc[k - 1])[0]); res["Z"].append(z)
+            k += 1
+        out = {k_: np.array(v) for k_, v in res.items()}
+        out["Z"] = out["Z"].reshape(-1, p["N"])
+        out["nmpc_info"] = out["nmpc_info"].reshape(-1, 3)
+        return out
+
     # ---- Kmpc.m:390-399 ---------------------------------------------------------------------------
     def resample_ref(self, ref):
         """The reference {t, y} resampled at the model's sampling time: tr = 0 : Ts : t(end), interp1(t, y, tr)."""
@@ -322,8 +350,9 @@ class Kmpc:
         through resample_ref.  y0s / u0s: (trials, n) / (trials, m) initial outputs and inputs (None: zeros; one row serves
         every trial).  Returns a list with one dict per trial: run_simulation's fields T, U, Y, K, R, Z scaled up, cut
         behind the last completed step, steps_done, and comp_time = the kernel's time divided by the steps it ran, for
-        every step.  Models with delays, loaded models and controllers with state bounds have no device loop: they run
-        through run_simulation, trial by trial."""
+        every step.  Models with delays, loaded models and linear / bilinear controllers with state bounds have no device
+        loop: they run through run_simulation, trial by trial.  Nonlinear controllers run in one launch too
+        (kp_nmpc_simulate, state bounds included) and add nmpc_info per trial."""
         p = self.params
         n, m = p["n"], p["m"]
         s = self.sysid
@@ -338,7 +367,9 @@ class Kmpc:
                 raise ValueError(f"{name} has {len(a)} entries for {nb} trials")
         y0s = np.zeros((nb, n)) if y0s is None else np.broadcast_to(y0s, (nb, n))
         u0s = np.zeros((nb, m)) if u0s is None else np.broadcast_to(u0s, (nb, m))
-        if (self.model_type == "nonlinear" or self.loaded or self.state_bounds is not None or int(p.get("nd", 0)) > 0):
+        if self.model_type == "nonlinear":
+            return self._run_simulations_nonlinear(ref_list, y0s, u0s)
+        if (self.loaded or self.state_bounds is not None or int(p.get("nd", 0)) > 0):
             out = []
             for i in range(nb):
                 r = self.run_simulation(ref_list[i if len(ref_list) > 1 else 0], y0s[i], u0s[i])
@@ -362,6 +393,32 @@ class Kmpc:
             out.append({"T": np.arange(k) * p["Ts"], "U": np.vstack([u0s[i:i + 1], s.scaleup_u(U[i, 1:k])]),
                         "Y": np.vstack([y0s[i:i + 1], s.scaleup_y(Y[i, 1:k])]), "K": np.arange(k), "R": R,
                         "Z": Z[i, :k - 1].copy(), "comp_time": np.full(k - 1, per_step), "steps_done": int(sd[i])})
+        return out
+
+    def _run_simulations_nonlinear(self, ref_list, y0s, u0s):
+        """run_simulations for a nonlinear controller: every trial's loop in ONE launch (kp_nmpc_simulate), state bounds
+        included; warm = nmpc_warm_start.  Each dict also holds nmpc_info, (SQP iterations, KKT residual, status) per step."""
+        from . import _ffi as F
+        p, s = self.params, self.sysid
+        nb = y0s.shape[0]
+        if any(r.shape != ref_list[0].shape for r in ref_list):
+            raise ValueError("run_simulations: every reference must have the same number of rows")
+        ref_sc = self.scaledown_ref(ref_list[0]) if len(ref_list) == 1 else np.stack([self.scaledown_ref(r) for r in ref_list])
+        U, Y, info, sd, st = self.dev.simulate(ref_sc, s.scaledown_y(y0s), s.scaledown_u(u0s), bool(self.nmpc_warm_start))
+        steps = int(sd.sum())
+        per_step = self.ctx.timer(F.TIMER_NMPC_SIM) * 1e-3 / steps if steps else 0.0
+        N, n = p["N"], p["n"]
+        out = []
+        for i in range(nb):
+            k = int(sd[i]) + 1                                         # rows 0 .. steps_done
+            ref_i = ref_list[i if len(ref_list) > 1 else 0]
+            rs = ref_sc if ref_sc.ndim == 2 else ref_sc[i]
+            R = np.vstack([ref_i[:1], self.scaleup_ref(rs[:k - 1])]) if k > 1 else ref_i[:1].copy()
+            Z = np.zeros((k - 1, N))
+            Z[:, :n] = Y[i, :k - 1]                                    # [zeta; 0] as get_mpcInput_nonlinear returns it (Kmpc.m:1180)
+            out.append({"T": np.arange(k) * p["Ts"], "U": np.vstack([u0s[i:i + 1], s.scaleup_u(U[i, 1:k])]),
+                        "Y": np.vstack([y0s[i:i + 1], s.scaleup_y(Y[i, 1:k])]), "K": np.arange(k), "R": R, "Z": Z,
+                        "comp_time": np.full(k - 1, per_step), "nmpc_info": info[i, :k - 1].copy(), "steps_done": int(sd[i])})
         return out
 
 
