@@ -101,7 +101,9 @@ int kp_device_info(const kp_ctx* ctx, char* name, int name_len, int* num_cu, int
  * once), 0 the order slot = job (a dictionary with more than 256 such jobs, the forms without the in-kernel monomial lift, the
  * KP_GRAM3_NOTUP form).  The results do not depend on it, bit for bit; environment variable KP_GRAM3_LIFT_ORDER=0 (read once) keeps
  * order 0 everywhere for A/B runs and tests.  21: the kernel of the most recent batch of nonlinear closed loops (kp_nmpc_simulate,
- * koopman_hip_nmpc.h), ms. */
+ * koopman_hip_nmpc.h), ms.  22: the kernel of the most recent batched eigensolver call (kp_eig, koopman_hip_spectrum.h), ms.  23: not
+ * a time - the regime that call ran: 1 a wave per matrix, 2 a workgroup with the matrix in LDS, 3 a workgroup with the matrix in a
+ * workspace slot; environment variable KP_EIG_REGIME (read per call) forces 2 or 3 for A/B runs and tests. */
 int kp_timer_get(const kp_ctx* ctx, int which, double* ms);
 /* Device pointer + byte size of the library stream's raw handle, for profilers/benchmarks
  * that want to bracket work with their own HIP events: returns hipStream_t as void*. */

@@ -1,12 +1,14 @@
 """Command line: identify a Koopman model from a reference data file, without MATLAB.
 
     python -m koopman_realizations_amd sysid DATA.mat --model_type bilinear --obs_degree 3 [--dim_red]
-        [--time_type continuous] [--lasso 1 10 100 --metric euclid_mean] [--out model.npz]
+        [--time_type continuous] [--lasso 1 10 100 --metric euclid_mean] [--spectrum] [--out model.npz]
 
 is example_sysid.m:22-65 (Ksysid constructor, train_models, validation of every `val` trial) with the options of
 Ksysid_setup.m; prints the validation errors and optionally stores the model matrices.  With several --lasso values every
 candidate is validated on every trial (one device call, Ksysid.val_candidates), the candidate with the least --metric is
-chosen (Ksysid.select_model) and that one is reported and stored."""
+chosen (Ksysid.select_model) and that one is reported and stored.  --spectrum prints the spectral radius, stability and the
+five leading eigenvalues of every candidate (one device call, Ksysid.candidate_spectra) and stores the chosen model's
+eigenvalues with --out."""
 from __future__ import annotations
 
 import argparse
@@ -33,6 +35,8 @@ def main(argv=None):
     s.add_argument("--time_type", default="discrete", choices=["discrete", "continuous"],
                    help="continuous: models of the matrix logarithm, validated by ode45 per sample interval (also one device call)")
     s.add_argument("--device", type=int, default=0)
+    s.add_argument("--spectrum", action="store_true",
+                   help="print radius, stability and the five leading eigenvalues of every candidate (linear / bilinear models)")
     s.add_argument("--out", default=None, help="write the model (A, B, C, K, scale) to this .npz")
     a = ap.parse_args(argv)
 
@@ -62,10 +66,20 @@ def main(argv=None):
         print(f"chosen by {a.metric}: candidate {best} (lasso {tab['lasso'][best]:g})")
     else:
         lines(0, "")
+    extra = {}
+    if a.spectrum and (a.model_type == "nonlinear" or a.loaded):
+        print("--spectrum: not available for nonlinear or loaded models (Ksysid.spectrum covers linear and bilinear ones)")
+    elif a.spectrum:
+        cs = ks.candidate_spectra()         # every candidate: one device call
+        for c in range(len(cs["radius"])):
+            lead = "  ".join(f"{z.real:.5f}{z.imag:+.5f}j" for z in cs["lam"][c][:5])
+            print(f"spectrum of candidate {c}: radius {cs['radius'][c]:.6f}  stable {bool(cs['stable'][c])}  leading {lead}")
+        cands = ks.candidates if many else [ks.candidates]
+        extra["lam"] = cs["lam"][[i for i, c in enumerate(cands) if c is ks.model][0]]
     if a.out:
         m = ks.model
         np.savez(a.out, **{k: np.asarray(m[k]) for k in ("A", "B", "C", "K", "Kf", "M") if k in m},
-                 **{"scale_" + k: v for k, v in p["scale"].items()})
+                 **{"scale_" + k: v for k, v in p["scale"].items()}, **extra)
         print("wrote", a.out)
     return 0
 

@@ -197,6 +197,16 @@ SIM_SIGNATURES = {
 }
 TIMER_MPC_SIM = 19                 # kp_timer_get slot: the kernel of the most recent kp_mpc_simulate, ms
 
+# the Koopman spectrum: batched eigenvalues and eigenvectors of general matrices (include/koopman_hip_spectrum.h)
+SPECTRUM_SIGNATURES = {
+    "kp_eig": (C.c_int, [vp, C.c_int, C.c_int, c_dp, C.c_int, c_dp, c_dp, c_dp, c_ip, c_ip]),
+}
+TIMER_EIG = 22                     # kp_timer_get slot: the kernel of the most recent kp_eig, ms
+TIMER_EIG_REGIME = 23              # ... and the regime it ran (1 wave per matrix, 2 workgroup in LDS, 3 workgroup in a workspace slot)
+EIG_MAXN = 512                     # KP_EIG_MAXN
+EIG_WAVE_MAX = 32                  # KP_EIG_WAVE_MAX
+EIG_LDS_MAXN_VEC, EIG_LDS_MAXN_VAL = 99, 140      # KP_EIG_LDS_MAXN_VEC, KP_EIG_LDS_MAXN_VAL
+
 _lib = None
 
 
@@ -209,7 +219,7 @@ def lib():
                           "(make -C koopman-realizations_amd/csrc)")
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in (SIGNATURES | NMPC_SIGNATURES | OBSERVER_SIGNATURES | CT_SIGNATURES | ARM_SIGNATURES
-                                   | RSYS_SIGNATURES | VALIDATE_SIGNATURES | SIM_SIGNATURES).items():
+                                   | RSYS_SIGNATURES | VALIDATE_SIGNATURES | SIM_SIGNATURES | SPECTRUM_SIGNATURES).items():
             fn = getattr(l, name)
             fn.restype, fn.argtypes = res, args
         _lib = l

@@ -154,7 +154,7 @@ void* kp_pinned_scratch(kp_ctx* ctx, size_t bytes) {
 }
 
 extern "C" int kp_timer_get(const kp_ctx* c, int which, double* ms) {
-  if (!c || !ms || which < 0 || which >= 22) return KP_ERR_ARG;
+  if (!c || !ms || which < 0 || which >= 24) return KP_ERR_ARG;
   *ms = c->timers[which];
   return KP_OK;
 }

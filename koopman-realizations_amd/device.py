@@ -13,6 +13,28 @@ import numpy as np
 from . import _ffi as F
 
 
+def eig_unpack(wr, wi, Vp):
+    """The raw outputs of kp_eig, wr / wi (nb, n) and Vp (nb, n, n) with Vp[b][:, j] column j of the packed real form (or
+    None), as complex arrays sorted per matrix by decreasing modulus.  The sort is stable on the device's order and ties in
+    modulus keep a pair together, the positive imaginary part first."""
+    lam = wr + 1j * wi
+    V = None
+    if Vp is not None:
+        V = Vp.astype(complex)
+        bs, js = np.nonzero(wi > 0)
+        re, im = Vp[bs, :, js], Vp[bs, :, js + 1]
+        V[bs, :, js] = re + 1j * im
+        V[bs, :, js + 1] = re - 1j * im
+    mod = np.abs(lam)
+    second = wi < 0                              # the second of a pair takes the modulus of the first: one float, no tie-break by rounding
+    mod[second] = np.roll(mod, 1, axis=1)[second]
+    order = np.argsort(-mod, axis=1, kind="stable")          # a matrix that failed is all NaN and keeps its order
+    lam = np.take_along_axis(lam, order, axis=1)
+    if V is not None:
+        V = np.take_along_axis(V, order[:, None, :], axis=2)
+    return lam, V
+
+
 class Context:
     """kp_ctx: one per process/GPU (one process per GPU in multi-GPU runs)."""
 
@@ -235,6 +257,29 @@ class Context:
                                 nsq.ctypes.data_as(F.c_ip), st.ctypes.data_as(F.c_ip)), self._h)
         L = np.transpose(L, (0, 2, 1))
         return (L[0], int(nsq[0]), int(st[0])) if single else (L, nsq, st)
+
+    def eig(self, A, vectors=True):
+        """kp_eig: eigenvalues and right eigenvectors of one n x n real matrix or a stack (nb, n, n), one device call.
+        Returns (lam, V, iters, status): lam complex, sorted per matrix by decreasing modulus with the positive imaginary part
+        of a pair first; V complex with unit columns in that order (None without `vectors`); lam and V NaN and status
+        KP_ERR_NOT_CONVERGED for a matrix with a non-finite entry or an eigenvalue that did not deflate."""
+        A = np.asarray(A, dtype=np.float64)
+        single = A.ndim == 2
+        if single:
+            A = A[None]
+        if A.ndim != 3 or A.shape[2] != A.shape[1]:
+            raise ValueError("kp_eig: square matrices only")
+        nb, n = A.shape[0], A.shape[1]
+        Ac = np.ascontiguousarray(np.transpose(A, (0, 2, 1)))        # each matrix column-major
+        wr = np.zeros((nb, n)); wi = np.zeros((nb, n))
+        Vp = np.zeros((nb, n, n)) if vectors else None
+        it = np.zeros(nb, dtype=np.int32); st = np.zeros(nb, dtype=np.int32)
+        F.check(F.lib().kp_eig(self._h, nb, n, F.dptr(Ac), int(bool(vectors)), F.dptr(wr), F.dptr(wi), F.dptr(Vp),
+                               it.ctypes.data_as(F.c_ip), st.ctypes.data_as(F.c_ip)), self._h)
+        lam, V = eig_unpack(wr, wi, None if Vp is None else np.transpose(Vp, (0, 2, 1)))
+        if single:
+            return lam[0], (None if V is None else V[0]), int(it[0]), int(st[0])
+        return lam, V, it, st
 
     def rollout_ct(self, model_type, A, B, z0, U, n_out, Ts, rtol=1e-3, atol=1e-6):
         """kp_rollout_ct: ode45 over every sample interval of z' = A z + B u (linear) or A z + sum_i u_i B_i z (bilinear),

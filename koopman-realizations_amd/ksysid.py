@@ -897,11 +897,12 @@ class Ksysid:
 
     _TABLE_METRICS = ("mean", "rmse", "nrmse", "euclid_mean", "unscaled_euclid_mean")
 
-    def select_model(self, metric="euclid_mean", table=None):
+    def select_model(self, metric="euclid_mean", table=None, require_stable=False):
         """The choice the reference leaves to the user (Ksysid.m:1384-1386): the candidate whose `metric`, averaged over the
         validation trials (and the outputs, for mean / rmse / nrmse), is least.  Candidates that diverged on a trial, or
         whose average is NaN, rank last.  table: a val_candidates result (default: computed now).  Sets self.model and
-        returns (index, table); ValueError when no candidate stays finite."""
+        returns (index, table); ValueError when no candidate stays finite.  require_stable: candidates whose spectrum is not
+        stable (candidate_spectra: one device call; a "stable" entry of the table is taken instead) rank last as well."""
         if metric not in self._TABLE_METRICS:
             raise ValueError(f"metric must be one of {self._TABLE_METRICS}")
         if table is None:
@@ -915,11 +916,95 @@ class Ksysid:
         with np.errstate(invalid="ignore", over="ignore"):
             score = vals.reshape(nmod, -1).mean(axis=1)
         bad = np.asarray(table["diverged"], dtype=bool).reshape(nmod, -1).any(axis=1) | ~np.isfinite(score)
+        if require_stable:
+            stable = table["stable"] if "stable" in table else self.candidate_spectra(cands)["stable"]
+            bad = bad | ~np.asarray(stable, dtype=bool).reshape(nmod)
         if bad.all():
-            raise ValueError("every candidate diverged on the validation trials")
+            raise ValueError("every candidate diverged on the validation trials" + (" or is unstable" if require_stable else ""))
         best = int(np.argmin(np.where(bad, np.inf, score)))
         self.model = cands[best]
         return best, table
+
+    # ---- spectrum (kp_eig, include/koopman_hip_spectrum.h) --------------------------------------------------
+    def _spectrum_A(self, model):
+        """The square operator on the lifted state whose spectrum is the model's: A of a linear model, A of a bilinear one
+        (its u = 0 dynamics)."""
+        if self.model_type == "nonlinear" or "A" not in model:
+            raise ValueError("spectrum: a nonlinear model's Kf is not a square operator on the lifted state")
+        if self.loaded:
+            raise NotImplementedError("spectrum: loaded models are not covered")
+        A = np.asarray(model["A"], dtype=np.float64)
+        if A.shape[0] > F.EIG_MAXN:
+            raise ValueError(f"spectrum: N = {A.shape[0]} exceeds the eigensolver's limit of {F.EIG_MAXN}")
+        return A
+
+    def _spectral_summary(self, lam, stable_tol):
+        """radius, exponent, decay, freq_hz, stable of eigenvalues lam (..., N); NaN eigenvalues are never stable."""
+        lam = np.asarray(lam, dtype=complex)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            exponent = lam.copy() if self.time_type == "continuous" else np.log(lam) / self.params["Ts"]
+            radius = np.abs(lam).max(axis=-1)
+            decay = exponent.real
+            stable = (decay.max(axis=-1) <= stable_tol) if self.time_type == "continuous" else (radius <= 1.0 + stable_tol)
+        return {"lam": lam, "radius": radius, "exponent": exponent, "decay": decay,
+                "freq_hz": np.abs(exponent.imag) / (2.0 * np.pi), "stable": stable}
+
+    def spectrum(self, model=None, vectors=True, stable_tol=1e-9):
+        """Eigenvalues, modes and left eigenvectors of a linear or bilinear model (for a bilinear one of A, the u = 0
+        dynamics), by the device eigensolver.  Returns a dict: lam (N, sorted by decreasing modulus, the positive imaginary
+        part of a pair first), radius = max |lam|, exponent (log(lam) / Ts of a discrete model, lam itself of a continuous one,
+        whose A is the generator), decay = Re exponent, freq_hz = |Im exponent| / 2 pi, stable (radius <= 1 + stable_tol, or
+        max decay <= stable_tol for a continuous model); with vectors V (unit columns), W = inv(V) (rows: the left
+        eigenvectors, W V = I; a host solve), cond_V and modes = C V (n x N, in scaled output units)."""
+        model = self.model if model is None else model
+        if model is None:
+            raise ValueError("no model: call train_models first")
+        A = self._spectrum_A(model)
+        lam, V, iters, status = self.ctx.eig(A, vectors=vectors)
+        if status != F.KP_OK:
+            raise F.KoopmanHipError(F.KP_ERR_NOT_CONVERGED, "spectrum: the eigensolver did not converge (a non-finite A?)")
+        spec = self._spectral_summary(lam, stable_tol)
+        spec["radius"], spec["stable"] = float(spec["radius"]), bool(spec["stable"])
+        spec["iters"], spec["time_type"], spec["Ts"] = int(iters), self.time_type, self.params["Ts"]
+        if vectors:
+            spec["V"] = V
+            spec["W"] = np.linalg.solve(V, np.eye(V.shape[0], dtype=complex))
+            spec["cond_V"] = float(np.linalg.cond(V))
+            spec["modes"] = np.asarray(model["C"], dtype=np.float64) @ V
+        return spec
+
+    def eigenfunctions(self, zeta, spec):
+        """The Koopman eigenfunctions phi = W psi(zeta) of a spectrum with vectors, for one state (N,) or rows of states
+        (rows x N): along the unforced discrete model phi(zeta_{k+1}) = lam * phi(zeta_k)."""
+        psi = np.asarray(self.lift.econ_full(zeta), dtype=np.float64)
+        W = spec["W"]
+        return W @ psi if psi.ndim == 1 else psi @ W.T
+
+    def spectrum_predict(self, zeta0, steps, spec):
+        """The outputs of the unforced model from its modes, Re(modes (lam**k * W psi(zeta0))) for k = 0 .. steps, as rows
+        (steps + 1) x n; a continuous model evaluates exp(exponent k Ts) in place of lam**k."""
+        phi0 = self.eigenfunctions(np.ravel(zeta0), spec)
+        k = np.arange(int(steps) + 1)[:, None]
+        if spec.get("time_type", self.time_type) == "continuous":
+            growth = np.exp(spec["exponent"][None, :] * (k * spec.get("Ts", self.params["Ts"])))
+        else:
+            growth = spec["lam"][None, :] ** k
+        return np.real((growth * phi0[None, :]) @ spec["modes"].T)
+
+    def candidate_spectra(self, models=None, stable_tol=1e-9):
+        """The eigenvalues of every candidate in ONE device call, values only.  Returns {"lam": (nmod, N), "radius",
+        "stable" (nmod), "lasso" when every model carries it}; a candidate the eigensolver refuses is NaN and not stable."""
+        if models is None:
+            models = self.candidates if self.candidates is not None else self.model
+        if models is None:
+            raise ValueError("no model: call train_models first")
+        models = [models] if isinstance(models, dict) else list(models)
+        lam = self.ctx.eig(np.stack([self._spectrum_A(mo) for mo in models]), vectors=False)[0]
+        spec = self._spectral_summary(lam, stable_tol)
+        out = {"lam": spec["lam"], "radius": spec["radius"], "stable": spec["stable"]}
+        if all("lasso" in mo for mo in models):
+            out["lasso"] = np.array([float(mo["lasso"]) for mo in models])
+        return out
 
     # ---- load observer (Ksysid.m:1975-2139) ------------------------------------------------------------
     def _observer_model(self):
