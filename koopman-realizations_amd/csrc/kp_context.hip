@@ -153,6 +153,14 @@ void* kp_pinned_scratch(kp_ctx* ctx, size_t bytes) {
   return ctx->pin_scratch;
 }
 
+int kp_dev_alloc_copy(kp_ctx* ctx, double** dst, const double* src, size_t n) {
+  *dst = nullptr;
+  if (!n) return KP_OK;
+  KP_HIP(ctx, hipMalloc((void**)dst, n * 8));
+  if (src) KP_HIP(ctx, hipMemcpy(*dst, src, n * 8, hipMemcpyHostToDevice));
+  return KP_OK;
+}
+
 extern "C" int kp_timer_get(const kp_ctx* c, int which, double* ms) {
   if (!c || !ms || which < 0 || which >= 24) return KP_ERR_ARG;
   *ms = c->timers[which];

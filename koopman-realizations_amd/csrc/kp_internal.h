@@ -218,6 +218,8 @@ struct kp_snapshots {
 };
 // page-locked host scratch of at least `bytes` (contents not preserved across calls that grow it); nullptr on failure
 void* kp_pinned_scratch(kp_ctx* ctx, size_t bytes);
+// a device array of n doubles in *dst (nullptr when n = 0), filled from src unless src is nullptr (kp_context.hip)
+int kp_dev_alloc_copy(kp_ctx* ctx, double** dst, const double* src, size_t n);
 void kp_stage_destroy(kp_ctx* ctx);
 void kp_host_free_all(kp_ctx* ctx);
 void kp_traj_pool_free(kp_ctx* ctx);

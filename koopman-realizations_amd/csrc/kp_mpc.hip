@@ -21,6 +21,7 @@
 #include "kp_internal.h"
 #include "koopman_hip_sim.h"
 #include "kp_wg_inverse.h"
+#include "kp_sim_loop.h"
 #include <type_traits>
 
 #include "kp_qp.h"
@@ -1027,21 +1028,17 @@ __global__ __launch_bounds__(256, 4) void kp_mpc_step_batch_kernel(MpcArgs a) {
   mpc_step_body<false>(a);
 }
 
-// ---- whole closed loops with the model as the plant (kp_mpc_simulate; Kmpc.run_simulation, Kmpc.m:403-512) -----------
-// One workgroup per trial runs steps k = 1 .. nref - 1 of the loop in scaled units: lift of Y[k-1], the step against rows
-// k-1 .. k-1+Np of the reference (its last row repeated behind its end, :354-365, :473-477) with u_prev = U[k-1], then
-// U[k] = the solution's second row and Y[k] = (A z + B u_prev)[0:n] or (A z + sum_i u_prev,i B_i z)[0:n] (the one-step input
-// delay of :495-496; C = [I 0], and only those n rows are ever read: the next step lifts Y[k] again).  A failed QP ends
-// the trial (the break of :483-485).
+// ---- whole closed loops with the model as the plant (kp_mpc_simulate; the loop's contract: kp_sim_loop.h) ---------------
+// The step is the QP step of kp_mpc_step_zeta: lift of Y[k-1], then the solve against the reference window.  The plant step
+// is Y[k] = (A z + B u_prev)[0:n] or (A z + sum_i u_prev,i B_i z)[0:n] (C = [I 0], and only those n rows are ever read: the
+// next step lifts Y[k] again).  Z rows are the lifted states.
 // Everything the loop carries lives in LDS behind the step's own block, at sim_off (offsets in doubles, each even):
-//   y n | u m | x nvar | ab (m + 1) n partial products of the model step | the reference with Np trailing copies of its last
-//   row ((nref + Np) nproj: every step's window is one contiguous block) | warm 1 + nvar ints: the trial's own optimal active
-//   set of the previous step | the dictionary's column descriptors | then P | PB at stage_off.
+//   y n | u m | x nvar | ab (m + 1) n partial products of the model step | the padded reference ((nref + Np) nproj) | warm
+//   1 + nvar ints: the trial's own optimal active set of the previous step | the dictionary's column descriptors | then
+//   P | PB at stage_off.
 // r and bq0 (m + nrows doubles) stay in global memory: a step asks for them with its first instructions and uses them
 // after the lift, as a single step does - nothing waits for them.
-// The step body takes these by plain LDS reads (its SIM mode): nothing that a step wrote is read through LDS-DMA.  No state
-// passes through global memory; U, Y and Z rows are only ever written.  A trial touches nothing that depends on blockIdx.x
-// except its own rows, so its result does not depend on nb or on its index.
+// The step body takes these by plain LDS reads (its SIM mode): nothing that a step wrote is read through LDS-DMA.
 struct SimLayout {
   int y, u, x, ab, ref, warm, cols, total;
 };
@@ -1059,16 +1056,14 @@ __host__ __device__ inline SimLayout sim_layout(int n, int m, int nv, int nproj,
   return L;
 }
 struct MpcSimArgs {
-  int nref, n, ref_shared, sim_off;
-  const double *ref, *y0, *u0;      // [nb or 1][nref][nproj], [nb][n], [nb][m]
-  double *U, *Y, *Z;                // [nb][nref][m], [nb][nref][n], [nb][nref - 1][N] or nullptr
-  int *steps_done, *status;         // [nb]
+  KpSimLoop loop;                   // (ny = n = the dictionary's nzeta, aux = Z, aux_w = N)
+  int sim_off;
 };
 __global__ __launch_bounds__(256) void kp_mpc_sim_kernel(MpcArgs a, MpcSimArgs sa) {
   extern __shared__ __align__(16) double sm[];
   const int tid = threadIdx.x;
-  const size_t trial = blockIdx.x;
-  const int N = a.N, m = a.m, Np = a.Np, nproj = a.nproj, nv = a.nvar, n = sa.n, nref = sa.nref;
+  const KpSimLoop& S = sa.loop;
+  const int N = a.N, m = a.m, Np = a.Np, nproj = a.nproj, nv = a.nvar, n = S.ny, nref = S.nref;
   const int nfull = a.basis.nfull;
   const SimLayout L = sim_layout(n, m, nv, nproj, Np, nref, nfull);
   double* sb = sm + sa.sim_off;
@@ -1078,9 +1073,6 @@ __global__ __launch_bounds__(256) void kp_mpc_sim_kernel(MpcArgs a, MpcSimArgs s
   double* refl = sb + L.ref;
   int* warm = (int*)(sb + L.warm);
   ColDesc* cols = (ColDesc*)(sb + L.cols);
-  double* Ut = sa.U + trial * (size_t)nref * m;
-  double* Yt = sa.Y + trial * (size_t)nref * n;
-  double* Zt = sa.Z ? sa.Z + trial * (size_t)(nref - 1) * N : nullptr;
   // ---- once per trial: what is constant over the run, the staged reference and row 0 ----
   if (a.stage_off) {          // P | PB by LDS-DMA, as a single step stages it
     typedef __attribute__((address_space(3))) char lds_char;
@@ -1091,45 +1083,28 @@ __global__ __launch_bounds__(256) void kp_mpc_sim_kernel(MpcArgs a, MpcSimArgs s
     for (int o = wbase; o < a.stage_doubles * 8; o += 256 * 16)
       __builtin_amdgcn_global_load_lds(src + o + lane16, dst + o, 16, 0, 0);
   }
-  {
-    const double* rt = sa.ref + (sa.ref_shared ? 0 : trial * (size_t)nref * nproj);
-    for (int e = tid; e < (nref + Np) * nproj; e += 256) {
-      const int row = e / nproj, p = e - row * nproj;
-      refl[e] = rt[(size_t)min(row, nref - 1) * nproj + p];
-    }
-    for (int e = tid; e < n; e += 256) {
-      const double v = sa.y0[trial * n + e];
-      y[e] = v;
-      Yt[e] = v;
-    }
-    for (int e = tid; e < m; e += 256) {
-      const double v = sa.u0[trial * m + e];
-      u[e] = v;
-      Ut[e] = v;
-    }
-    for (int e = tid; e < nfull; e += 256) cols[e] = a.basis.cols[e];
-    // cold first step: an empty set - and row ids of 0 behind it: a step asks for the constraint rows of ALL nvar ids before
-    // it knows the set's size (mpc_step_body: warm_row, then ell.val[k nrows + warm_row]), and LDS starts out as garbage
-    if (tid <= nv) warm[tid] = 0;           // (nvar <= 64)
-  }
+  const KpSimRows T = kp_sim_prologue(S, refl, y, u);
+  for (int e = tid; e < nfull; e += 256) cols[e] = a.basis.cols[e];
+  // cold first step: an empty set - and row ids of 0 behind it: a step asks for the constraint rows of ALL nvar ids before
+  // it knows the set's size (mpc_step_body: warm_row, then ell.val[k nrows + warm_row]), and LDS starts out as garbage
+  if (tid <= nv) warm[tid] = 0;             // (nvar <= 64)
   // the LDS-DMA above is counted by the vector-memory counter, which a barrier does not wait for by itself
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   MpcArgs s = a;
   s.basis.cols = cols;
   s.warm = warm;
-  s.status = sa.status + trial;
+  s.status = S.status + blockIdx.x;
   MpcSimIn si;
   si.zeta = y;
   si.up = u;
   si.x = sb + L.x;
   si.z = sm;
   const bool bil = a.model_type == KP_MODEL_BILINEAR;
-  const double qnan = __builtin_nan("");
   int k = 1, failed = 0;
   for (; k < nref; ++k) {
     si.yr = refl + (size_t)(k - 1) * nproj;
-    s.z_out = Zt ? Zt + (size_t)(k - 1) * N : nullptr;
+    s.z_out = T.aux ? T.aux + (size_t)(k - 1) * N : nullptr;
     failed = mpc_step_body<true, false, true>(s, nullptr, &si);     // (ends behind a barrier: x, z and the status are visible)
     if (failed) break;                      // (uniform)
     // model step, rows 0 .. n-1: ab[j n + r] = row r of A (j = 0) or of B_j (bilinear, j = 1 .. m) times z, four lanes each
@@ -1147,7 +1122,7 @@ __global__ __launch_bounds__(256) void kp_mpc_sim_kernel(MpcArgs a, MpcSimArgs s
     }
     __syncthreads();
     double ynew = 0.0, unew = 0.0;
-    if (tid < n) {
+    if (tid < n) {                          // (n <= 256: kp_mpc_simulate)
       ynew = ab[tid];
       // (two loops where one conditional expression would do: see the compiler hazard in DESIGN 3.3h - with the single
       //  expression the hipcc of ROCm 7.2 places its copy of the LDS aperture register in VCC and stops with "Illegal
@@ -1159,38 +1134,14 @@ __global__ __launch_bounds__(256) void kp_mpc_sim_kernel(MpcArgs a, MpcSimArgs s
     }
     if (tid < m) unew = si.x[m + tid];      // the second row of the solution
     __syncthreads();                        // (every read of the old u is done)
-    if (tid < n) {
-      y[tid] = ynew;
-      Yt[(size_t)k * n + tid] = ynew;
-    }
-    if (tid < m) {
-      u[tid] = unew;
-      Ut[(size_t)k * m + tid] = unew;
-    }
+    kp_sim_commit(S, T, k, y, u, [&](int) { return ynew; }, [&](int) { return unew; });
     __syncthreads();                        // y, u and the body's arrays are free for the next step
   }
-  if (failed) {
-    // rows k .. nref-1 of U and Y and the lifted states from this step's on: NaN (the step wrote its z behind a barrier)
-    for (size_t e = (size_t)k * m + tid; e < (size_t)nref * m; e += 256) Ut[e] = qnan;
-    for (size_t e = (size_t)k * n + tid; e < (size_t)nref * n; e += 256) Yt[e] = qnan;
-    if (Zt)
-      for (size_t e = (size_t)(k - 1) * N + tid; e < (size_t)(nref - 1) * N; e += 256) Zt[e] = qnan;
-  }
-  if (tid == 0) {
-    sa.steps_done[trial] = k - 1;
-    sa.status[trial] = failed ? KP_ERR_QP_FAIL : KP_OK;
-  }
+  // (a failed step wrote its z behind a barrier: the NaN tail of Z starts at its row)
+  kp_sim_epilogue(S, T, k, failed, failed ? KP_ERR_QP_FAIL : KP_OK);
 }
 
 // ---- host API ------------------------------------------------------------------------------------
-
-static int dev_alloc_copy(kp_ctx* ctx, double** dst, const double* src, size_t n) {
-  *dst = nullptr;
-  if (!n) return KP_OK;
-  KP_HIP(ctx, hipMalloc((void**)dst, n * 8));
-  if (src) KP_HIP(ctx, hipMemcpy(*dst, src, n * 8, hipMemcpyHostToDevice));
-  return KP_OK;
-}
 
 extern "C" int kp_mpc_destroy(kp_mpc* M) {
   if (!M) return KP_OK;
@@ -1284,31 +1235,31 @@ extern "C" int kp_mpc_create(kp_ctx* ctx, int model_type, const double* A, const
   M->N = N; M->m = m; M->Np = Np; M->nproj = nproj; M->nvar = nvar; M->nrows = nrows;
   M->mb = model_type == KP_MODEL_BILINEAR ? N * m : m;
   M->q_run = q_run; M->q_term = q_term;
-  int rc = dev_alloc_copy(ctx, &M->A, A, (size_t)N * N);
-  if (!rc) rc = dev_alloc_copy(ctx, &M->B, B, (size_t)N * M->mb);
+  int rc = kp_dev_alloc_copy(ctx, &M->A, A, (size_t)N * N);
+  if (!rc) rc = kp_dev_alloc_copy(ctx, &M->B, B, (size_t)N * M->mb);
   // P | PB in ONE allocation (PB at an even offset), padded to a multiple of 4 KB: a single-problem step copies the block
   // to LDS with 1 KB loads per wave
   const size_t nP = ((size_t)(Np + 1) * nproj * N + 1) & ~(size_t)1;
   const size_t nPB = model_type == KP_MODEL_BILINEAR ? (size_t)Np * nproj * m * N : 0;
   M->stage_doubles = (int)((nP + nPB + 511) & ~(size_t)511);
-  if (!rc) rc = dev_alloc_copy(ctx, &M->P, nullptr, (size_t)M->stage_doubles);
+  if (!rc) rc = kp_dev_alloc_copy(ctx, &M->P, nullptr, (size_t)M->stage_doubles);
   if (!rc && nPB) M->PB = M->P + nP;
-  if (!rc) rc = dev_alloc_copy(ctx, &M->S0, nullptr, (size_t)Np * nproj * m);
-  if (!rc) rc = dev_alloc_copy(ctx, &M->r, r, m);
-  if (!rc) rc = dev_alloc_copy(ctx, &M->Aq, Aq.data(), Aq.size());
-  if (!rc) rc = dev_alloc_copy(ctx, &M->bq0, bq.data(), nrows);
+  if (!rc) rc = kp_dev_alloc_copy(ctx, &M->S0, nullptr, (size_t)Np * nproj * m);
+  if (!rc) rc = kp_dev_alloc_copy(ctx, &M->r, r, m);
+  if (!rc) rc = kp_dev_alloc_copy(ctx, &M->Aq, Aq.data(), Aq.size());
+  if (!rc) rc = kp_dev_alloc_copy(ctx, &M->bq0, bq.data(), nrows);
   std::vector<double> ev, en;
   std::vector<int> ec;
   to_ell(Aq.data(), nrows, nvar, ev, ec, en, M->ellK);
-  if (!rc) rc = dev_alloc_copy(ctx, &M->Anorm, en.data(), nrows);
-  if (!rc) rc = dev_alloc_copy(ctx, &M->ellv, ev.data(), ev.size());
+  if (!rc) rc = kp_dev_alloc_copy(ctx, &M->Anorm, en.data(), nrows);
+  if (!rc) rc = kp_dev_alloc_copy(ctx, &M->ellv, ev.data(), ev.size());
   if (!rc) {
     hipError_t e2 = hipMalloc((void**)&M->ellc, ec.size() * 4);
     if (e2 == hipSuccess) e2 = hipMemcpy(M->ellc, ec.data(), ec.size() * 4, hipMemcpyHostToDevice);
     if (e2 != hipSuccess) rc = ctx->fail(KP_ERR_HIP, std::string("kp_mpc_create: ") + hipGetErrorString(e2));
   }
   double* dproj = nullptr;
-  if (!rc) rc = dev_alloc_copy(ctx, &dproj, proj, (size_t)nproj * N);
+  if (!rc) rc = kp_dev_alloc_copy(ctx, &dproj, proj, (size_t)nproj * N);
   if (rc) {
     if (dproj) (void)hipFree(dproj);
     kp_mpc_destroy(M);
@@ -1442,7 +1393,7 @@ extern "C" int kp_mpc_set_state_bounds(kp_mpc* M, int n, const double* lo, const
   const int mr = M->nrows + 2 * n * (Np + 1);
   std::vector<double> lh(2 * n);
   for (int i = 0; i < n; ++i) { lh[i] = lo[i]; lh[n + i] = hi[i]; }
-  int rc = dev_alloc_copy(ctx, &M->sb_lohi, lh.data(), lh.size());
+  int rc = kp_dev_alloc_copy(ctx, &M->sb_lohi, lh.data(), lh.size());
   if (rc) return rc;
   KP_HIP(ctx, hipMalloc((void**)&M->sb_Apow, (size_t)(kmax + 1) * N * N * 8));
   std::vector<double> eye((size_t)N * N, 0.0);
@@ -1761,10 +1712,7 @@ extern "C" int kp_mpc_step_batch(kp_mpc* M, int nb, const double* z, const doubl
   return mpc_run(M, nullptr, nb, z, nullptr, u_prev, Yr, 1, U_out, nullptr, status);
 }
 
-// Whole closed loops, one workgroup per trial (kp_mpc_sim_kernel).  Small calls (a single trial of a few hundred steps)
-// are latency bound: inputs and outputs each cross in ONE copy through the page-locked scratch.  Large batches are
-// bandwidth bound: their outputs go straight to the caller's arrays instead of through a second host copy.
-#define KP_SIM_PINNED_BYTES ((size_t)4 << 20)
+// Whole closed loops, one workgroup per trial (kp_mpc_sim_kernel); the host transfers are kp_sim_loop.h's.
 extern "C" int kp_mpc_simulate(kp_mpc* M, const kp_basis* basis, int nb, int nref, const double* ref, int ref_shared,
                                const double* y0, const double* u0, int iters, double* U, double* Y, double* Z, int* steps_done,
                                int* status) {
@@ -1815,56 +1763,18 @@ extern "C" int kp_mpc_simulate(kp_mpc* M, const kp_basis* basis, int nb, int nre
     a.stage_off = (int)((lds / 8 + 1) & ~(size_t)1);
     lds = (size_t)(a.stage_off + M->stage_doubles) * 8;
   }
-  // device block: [ref | y0 | u0] | U | Y | Z | steps_done, status
-  const size_t nR = (size_t)(ref_shared ? 1 : nb) * nref * nproj, nY0 = (size_t)nb * n, nU0 = (size_t)nb * m, n_in = nR + nY0 + nU0;
-  const size_t nU = (size_t)nb * nref * m, nY = (size_t)nb * nref * n, nZ = Z ? (size_t)nb * (nref - 1) * N : 0;
-  const size_t n_int = ((size_t)2 * nb + 1) / 2, n_out = nU + nY + nZ + n_int;
-  double* ws = (double*)ctx->workspace(6, (n_in + n_out) * 8);
-  if (!ws) return ctx->fail(KP_ERR_HIP, "kp_mpc_simulate: out of device memory");
-  const bool pinned = (n_in + n_out) * 8 <= KP_SIM_PINNED_BYTES;
-  std::vector<double> h_vec;
-  double* h = nullptr;
-  if (pinned) {
-    h = (double*)kp_pinned_scratch(ctx, (n_in + n_out) * 8);
-    if (!h) return ctx->fail(KP_ERR_HIP, "kp_mpc_simulate: out of page-locked memory");
-  } else {
-    h_vec.resize(n_in);
-    h = h_vec.data();
-  }
-  memcpy(h, ref, nR * 8);
-  memcpy(h + nR, y0, nY0 * 8);
-  memcpy(h + nR + nY0, u0, nU0 * 8);
+  KpSimLoop& S = sa.loop;
+  S.nref = nref; S.ny = n; S.m = m; S.nproj = nproj; S.Np = Np; S.ref_shared = ref_shared ? 1 : 0; S.aux_w = Z ? N : 0;
+  KpSimIo io;
+  if (int rcu = kp_sim_upload(ctx, "kp_mpc_simulate", nb, ref, y0, u0, S, io)) return rcu;
   hipStream_t s = ctx->stream;
-  KP_HIP(ctx, hipMemcpyAsync(ws, h, n_in * 8, hipMemcpyHostToDevice, s));
-  double* d_out = ws + n_in;
-  sa.nref = nref; sa.n = n; sa.ref_shared = ref_shared ? 1 : 0;
-  sa.ref = ws; sa.y0 = ws + nR; sa.u0 = ws + nR + nY0;
-  sa.U = d_out; sa.Y = d_out + nU; sa.Z = nZ ? d_out + nU + nY : nullptr;
-  sa.steps_done = (int*)(d_out + nU + nY + nZ);
-  sa.status = sa.steps_done + nb;
   static KpLdsCache sim_lds;
   KP_HIP(ctx, kp_ensure_lds(sim_lds, (const void*)kp_mpc_sim_kernel, lds));
   KP_HIP(ctx, hipEventRecord(ctx->evp[4], s));
   hipLaunchKernelGGL(kp_mpc_sim_kernel, dim3(nb), dim3(256), lds, s, a, sa);
   KP_HIP(ctx, hipGetLastError());
   KP_HIP(ctx, hipEventRecord(ctx->evp[5], s));
-  if (pinned) {
-    double* h_out = h + n_in;
-    KP_HIP(ctx, hipMemcpyAsync(h_out, d_out, n_out * 8, hipMemcpyDeviceToHost, s));
-    KP_HIP(ctx, hipStreamSynchronize(s));
-    memcpy(U, h_out, nU * 8);
-    memcpy(Y, h_out + nU, nY * 8);
-    if (nZ) memcpy(Z, h_out + nU + nY, nZ * 8);
-    memcpy(steps_done, h_out + nU + nY + nZ, (size_t)nb * sizeof(int));
-    memcpy(status, (const int*)(h_out + nU + nY + nZ) + nb, (size_t)nb * sizeof(int));
-  } else {
-    KP_HIP(ctx, hipMemcpyAsync(U, sa.U, nU * 8, hipMemcpyDeviceToHost, s));
-    KP_HIP(ctx, hipMemcpyAsync(Y, sa.Y, nY * 8, hipMemcpyDeviceToHost, s));
-    if (nZ) KP_HIP(ctx, hipMemcpyAsync(Z, sa.Z, nZ * 8, hipMemcpyDeviceToHost, s));
-    KP_HIP(ctx, hipMemcpyAsync(steps_done, sa.steps_done, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s));
-    KP_HIP(ctx, hipMemcpyAsync(status, sa.status, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s));
-    KP_HIP(ctx, hipStreamSynchronize(s));
-  }
+  if (int rcd = kp_sim_download(ctx, io, S, U, Y, Z, steps_done, status)) return rcd;
   float ms = 0;
   if (hipEventElapsedTime(&ms, ctx->evp[4], ctx->evp[5]) == hipSuccess) ctx->timers[19] = ms;
   return KP_OK;

@@ -33,6 +33,7 @@
 #include "koopman_hip_nmpc.h"
 #include "kp_wg_inverse.h"
 #include "kp_qp.h"
+#include "kp_sim_loop.h"
 
 #define NMPC_CHUNK 16           // dictionary columns whose gradients are staged per pass of the Jacobian
 #define NMPC_LDS_MAX (160 * 1024)
@@ -617,55 +618,31 @@ __global__ __launch_bounds__(256) void kp_nmpc_kernel(NmpcArgs a) {
   }
 }
 
-// ---- whole closed loops with the model as the plant (kp_nmpc_simulate; Kmpc.run_simulation, Kmpc.m:403-512) -----------
-// One workgroup per trial runs steps k = 1 .. nref - 1 in scaled units: the SQP of kp_nmpc_step at zeta = Y[k-1],
-// u_prev = U[k-1] against rows k-1 .. k-1+Np of the reference (its last row repeated behind its end, :354-365), then
-// U[k] = the solution's second row and Y[k] = z_1 of the solution's rollout = F(zeta, u_prev), because u_1 is pinned to u_prev:
-// the one-step input delay of :495-496.  mu and the damping restart at every step, as in separate launches.
-// Staged once per trial: Kfull, the reference with Np trailing copies of its last row behind the step's block (at sim_off:
-// every step's window is one contiguous block) and, with state bounds, the constant linear rows of the trial's dense
-// constraint matrix.  zeta, u_prev and the previous solution U stay in the step's own LDS blocks from one step to the next;
-// U, Y and info rows are only ever written.  A failed QP subproblem ends the trial (the break of :483-485); an unconverged
-// step returns its last iterate and the trial goes on.  A trial touches nothing that depends on blockIdx.x except its own
-// rows, so its result does not depend on nb or on its index.  Every loop is bounded by nref, max_iter and NMPC_LS_MAX.
+// ---- whole closed loops with the model as the plant (kp_nmpc_simulate; the loop's contract: kp_sim_loop.h) ---------------
+// The step is the SQP of kp_nmpc_step; the plant step is Y[k] = z_1 of the solution's rollout = F(zeta, u_prev), because
+// u_1 is pinned to u_prev.  mu and the damping restart at every step, as in separate launches.
+// Staged once per trial besides the padded reference (behind the step's block, at sim_off): Kfull and, with state bounds,
+// the constant linear rows of the trial's dense constraint matrix.  zeta, u_prev and the previous solution U stay in the
+// step's own LDS blocks from one step to the next.  Only a failed QP subproblem ends the trial; an unconverged step returns
+// its last iterate, the trial goes on and its status becomes KP_ERR_NOT_CONVERGED.  The aux rows are info: SQP iterations,
+// KKT residual and status of every step.  Every loop is bounded by nref, max_iter and NMPC_LS_MAX.
 struct NmpcSimArgs {
-  int nref, ref_shared, warm, sim_off;
-  const double *ref, *y0, *u0;      // [nb or 1][nref][nproj], [nb][nz], [nb][m]
-  double *U, *Y, *info;             // [nb][nref][m], [nb][nref][nz], [nb][nref - 1][3] or nullptr
-  int *steps_done, *status;         // [nb]
+  KpSimLoop loop;                   // (ny = nz, aux = info, aux_w = 3)
+  int warm, sim_off;
 };
 __global__ __launch_bounds__(256) void kp_nmpc_sim_kernel(NmpcArgs a, NmpcSimArgs sa) {
   extern __shared__ __align__(16) double sm[];
   const int tid = threadIdx.x, pb = blockIdx.x;
   const size_t trial = blockIdx.x;
+  const KpSimLoop& S = sa.loop;
   const NmpcLayout& L = a.L;
-  const int nz = a.nz, m = a.m, Np = a.Np, nproj = a.nproj, nref = sa.nref, nfull = a.b.nfull;
+  const int nz = a.nz, m = a.m, nproj = a.nproj, nref = S.nref, nfull = a.b.nfull;
   double *Kfull = sm + L.Kfull, *zeta0 = sm + L.zeta0, *up = sm + L.up, *U = sm + L.U, *Z = sm + L.Z, *refl = sm + sa.sim_off;
-  double* Ut = sa.U + trial * (size_t)nref * m;
-  double* Yt = sa.Y + trial * (size_t)nref * nz;
-  double* It = sa.info ? sa.info + trial * (size_t)(nref - 1) * 3 : nullptr;
   // ---- once per trial ----
   for (int e = tid; e < nz * nfull; e += 256) Kfull[e] = a.Kfull[e];
-  {
-    const double* rt = sa.ref + (sa.ref_shared ? 0 : trial * (size_t)nref * nproj);
-    for (int e = tid; e < (nref + Np) * nproj; e += 256) {
-      const int row = e / nproj, p = e - row * nproj;
-      refl[e] = rt[(size_t)min(row, nref - 1) * nproj + p];
-    }
-  }
-  for (int e = tid; e < nz; e += 256) {
-    const double v = sa.y0[trial * nz + e];
-    zeta0[e] = v;
-    Yt[e] = v;
-  }
-  for (int e = tid; e < m; e += 256) {
-    const double v = sa.u0[trial * m + e];
-    up[e] = v;
-    Ut[e] = v;
-  }
+  const KpSimRows T = kp_sim_prologue(S, refl, zeta0, up);
   if (a.sb) nmpc_dense_lin_rows(a, a.dval + trial * (size_t)a.mr * a.nU, a.dnorm + trial * (size_t)a.mr);
   __syncthreads();
-  const double qnan = __builtin_nan("");
   int k = 1, failed = 0, unconverged = 0;
   for (; k < nref; ++k) {
     int it;
@@ -677,33 +654,16 @@ __global__ __launch_bounds__(256) void kp_nmpc_sim_kernel(NmpcArgs a, NmpcSimArg
     }
     unconverged |= st != KP_OK;
     __syncthreads();                        // (every read of zeta0 and up is done; U and Z are the step's results)
-    for (int e = tid; e < nz; e += 256) {
-      const double v = Z[nz + e];           // z_1 = F(zeta, u_prev)
-      zeta0[e] = v;
-      Yt[(size_t)k * nz + e] = v;
-    }
-    for (int e = tid; e < m; e += 256) {
-      const double v = U[m + e];            // the second row of the solution
-      up[e] = v;
-      Ut[(size_t)k * m + e] = v;
-    }
-    if (It && tid == 0) {
-      It[(size_t)(k - 1) * 3] = (double)it;
-      It[(size_t)(k - 1) * 3 + 1] = kkt;
-      It[(size_t)(k - 1) * 3 + 2] = (double)st;
+    kp_sim_commit(S, T, k, zeta0, up, [&](int e) { return Z[nz + e]; },      // z_1 = F(zeta, u_prev)
+                  [&](int e) { return U[m + e]; });                            // the second row of the solution
+    if (T.aux && tid == 0) {
+      T.aux[(size_t)(k - 1) * 3] = (double)it;
+      T.aux[(size_t)(k - 1) * 3 + 1] = kkt;
+      T.aux[(size_t)(k - 1) * 3 + 2] = (double)st;
     }
     __syncthreads();
   }
-  if (failed) {   // rows k .. nref-1 of U and Y and the info rows from this step's on: NaN
-    for (size_t e = (size_t)k * m + tid; e < (size_t)nref * m; e += 256) Ut[e] = qnan;
-    for (size_t e = (size_t)k * nz + tid; e < (size_t)nref * nz; e += 256) Yt[e] = qnan;
-    if (It)
-      for (size_t e = (size_t)(k - 1) * 3 + tid; e < (size_t)(nref - 1) * 3; e += 256) It[e] = qnan;
-  }
-  if (tid == 0) {
-    sa.steps_done[trial] = k - 1;
-    sa.status[trial] = failed ? KP_ERR_QP_FAIL : (unconverged ? KP_ERR_NOT_CONVERGED : KP_OK);
-  }
+  kp_sim_epilogue(S, T, k, failed, failed ? KP_ERR_QP_FAIL : (unconverged ? KP_ERR_NOT_CONVERGED : KP_OK));
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
@@ -726,14 +686,6 @@ struct kp_nmpc {
   unsigned long long step_seq = 0;
   double* jac = nullptr;                        // device: the Jacobians of the last single step
 };
-
-static int nm_alloc_copy(kp_ctx* ctx, double** dst, const double* src, size_t n) {
-  *dst = nullptr;
-  if (!n) return KP_OK;
-  KP_HIP(ctx, hipMalloc((void**)dst, n * 8));
-  if (src) KP_HIP(ctx, hipMemcpy(*dst, src, n * 8, hipMemcpyHostToDevice));
-  return KP_OK;
-}
 
 static int nmpc_rows(const kp_nmpc* M) { return M->nlin + (M->sb ? 2 * (M->Np + 1) * M->nz : 0); }
 
@@ -872,15 +824,15 @@ extern "C" int kp_nmpc_create(kp_ctx* ctx, const kp_basis* basis, const double* 
     return ctx->fail(KP_ERR_ARG, "kp_nmpc_create: the step's workspace (" + std::to_string(lds) + " bytes) exceeds the " +
                                      std::to_string(NMPC_LDS_MAX) + " bytes of LDS");
   }
-  int rc = nm_alloc_copy(ctx, &M->Kv, Kv.data(), Kv.size());
-  if (!rc) rc = nm_alloc_copy(ctx, &M->Kfull, Kfu.data(), Kfu.size());
-  if (!rc) rc = nm_alloc_copy(ctx, &M->cvec, cv.data(), cv.size());
-  if (!rc) rc = nm_alloc_copy(ctx, &M->proj, proj, (size_t)nproj * nz);
-  if (!rc) rc = nm_alloc_copy(ctx, &M->r, r, m);
-  if (!rc) rc = nm_alloc_copy(ctx, &M->lin_val, ev.data(), ev.size());
-  if (!rc) rc = nm_alloc_copy(ctx, &M->lin_b, bl.data(), bl.size());
-  if (!rc) rc = nm_alloc_copy(ctx, &M->lin_norm, en.data(), en.size());
-  if (!rc) rc = nm_alloc_copy(ctx, &M->jac, nullptr, (size_t)Np * nz * nv);
+  int rc = kp_dev_alloc_copy(ctx, &M->Kv, Kv.data(), Kv.size());
+  if (!rc) rc = kp_dev_alloc_copy(ctx, &M->Kfull, Kfu.data(), Kfu.size());
+  if (!rc) rc = kp_dev_alloc_copy(ctx, &M->cvec, cv.data(), cv.size());
+  if (!rc) rc = kp_dev_alloc_copy(ctx, &M->proj, proj, (size_t)nproj * nz);
+  if (!rc) rc = kp_dev_alloc_copy(ctx, &M->r, r, m);
+  if (!rc) rc = kp_dev_alloc_copy(ctx, &M->lin_val, ev.data(), ev.size());
+  if (!rc) rc = kp_dev_alloc_copy(ctx, &M->lin_b, bl.data(), bl.size());
+  if (!rc) rc = kp_dev_alloc_copy(ctx, &M->lin_norm, en.data(), en.size());
+  if (!rc) rc = kp_dev_alloc_copy(ctx, &M->jac, nullptr, (size_t)Np * nz * nv);
   if (!rc) {
     hipError_t e = hipMalloc((void**)&M->lin_col, ec.size() * 4);
     if (e == hipSuccess) e = hipMemcpy(M->lin_col, ec.data(), ec.size() * 4, hipMemcpyHostToDevice);
@@ -1042,10 +994,7 @@ extern "C" int kp_nmpc_step(kp_nmpc* M, const double* zeta, const double* u_prev
   return kp_nmpc_step_batch(M, 1, zeta, u_prev, Yr, U_init, U_out, Z_out, info, status);
 }
 
-// Whole closed loops, one workgroup per trial (kp_nmpc_sim_kernel).  Host transfers as kp_mpc_simulate: the inputs cross in
-// one packed copy; the outputs come back through the page-locked scratch in one copy up to 4 MB, else straight into the
-// caller's arrays.
-#define KP_NMPC_SIM_PINNED_BYTES ((size_t)4 << 20)
+// Whole closed loops, one workgroup per trial (kp_nmpc_sim_kernel); the host transfers are kp_sim_loop.h's.
 extern "C" int kp_nmpc_simulate(kp_nmpc* M, int nb, int nref, const double* ref, int ref_shared, const double* y0, const double* u0,
                                 int warm, double* U, double* Y, double* info, int* steps_done, int* status) {
   if (!M) return KP_ERR_ARG;
@@ -1081,56 +1030,19 @@ extern "C" int kp_nmpc_simulate(kp_nmpc* M, int nb, int nref, const double* ref,
   a.lin = EllMat{M->lin_val, M->lin_col, M->lin_norm, M->linK};
   a.lin_b = M->lin_b;
   a.dval = M->dval; a.dcol = M->dcol; a.dnorm = M->dnorm;
-  // device block: [ref | y0 | u0] | U | Y | info | steps_done, status
-  const size_t nR = (size_t)(ref_shared ? 1 : nb) * nref * nproj, nY0 = (size_t)nb * nz, nU0 = (size_t)nb * m, n_in = nR + nY0 + nU0;
-  const size_t nU = (size_t)nb * nref * m, nY = (size_t)nb * nref * nz, nI = info ? (size_t)nb * (nref - 1) * 3 : 0;
-  const size_t n_int = ((size_t)2 * nb + 1) / 2, n_out = nU + nY + nI + n_int;
-  double* ws = (double*)ctx->workspace(6, (n_in + n_out) * 8);
-  if (!ws) return ctx->fail(KP_ERR_HIP, "kp_nmpc_simulate: out of device memory");
-  const bool pinned = (n_in + n_out) * 8 <= KP_NMPC_SIM_PINNED_BYTES;
-  std::vector<double> h_vec;
-  double* h = nullptr;
-  if (pinned) {
-    h = (double*)kp_pinned_scratch(ctx, (n_in + n_out) * 8);
-    if (!h) return ctx->fail(KP_ERR_HIP, "kp_nmpc_simulate: out of page-locked memory");
-  } else {
-    h_vec.resize(n_in);
-    h = h_vec.data();
-  }
-  memcpy(h, ref, nR * 8);
-  memcpy(h + nR, y0, nY0 * 8);
-  memcpy(h + nR + nY0, u0, nU0 * 8);
+  sa.warm = warm ? 1 : 0;
+  KpSimLoop& S = sa.loop;
+  S.nref = nref; S.ny = nz; S.m = m; S.nproj = nproj; S.Np = Np; S.ref_shared = ref_shared ? 1 : 0; S.aux_w = info ? 3 : 0;
+  KpSimIo io;
+  if (int rcu = kp_sim_upload(ctx, "kp_nmpc_simulate", nb, ref, y0, u0, S, io)) return rcu;
   hipStream_t s = ctx->stream;
-  KP_HIP(ctx, hipMemcpyAsync(ws, h, n_in * 8, hipMemcpyHostToDevice, s));
-  double* d_out = ws + n_in;
-  sa.nref = nref; sa.ref_shared = ref_shared ? 1 : 0; sa.warm = warm ? 1 : 0;
-  sa.ref = ws; sa.y0 = ws + nR; sa.u0 = ws + nR + nY0;
-  sa.U = d_out; sa.Y = d_out + nU; sa.info = nI ? d_out + nU + nY : nullptr;
-  sa.steps_done = (int*)(d_out + nU + nY + nI);
-  sa.status = sa.steps_done + nb;
   static KpLdsCache sim_lds;
   KP_HIP(ctx, kp_ensure_lds(sim_lds, (const void*)kp_nmpc_sim_kernel, lds));
   KP_HIP(ctx, hipEventRecord(ctx->evp[4], s));
   hipLaunchKernelGGL(kp_nmpc_sim_kernel, dim3(nb), dim3(256), lds, s, a, sa);
   KP_HIP(ctx, hipGetLastError());
   KP_HIP(ctx, hipEventRecord(ctx->evp[5], s));
-  if (pinned) {
-    double* h_out = h + n_in;
-    KP_HIP(ctx, hipMemcpyAsync(h_out, d_out, n_out * 8, hipMemcpyDeviceToHost, s));
-    KP_HIP(ctx, hipStreamSynchronize(s));
-    memcpy(U, h_out, nU * 8);
-    memcpy(Y, h_out + nU, nY * 8);
-    if (nI) memcpy(info, h_out + nU + nY, nI * 8);
-    memcpy(steps_done, h_out + nU + nY + nI, (size_t)nb * sizeof(int));
-    memcpy(status, (const int*)(h_out + nU + nY + nI) + nb, (size_t)nb * sizeof(int));
-  } else {
-    KP_HIP(ctx, hipMemcpyAsync(U, sa.U, nU * 8, hipMemcpyDeviceToHost, s));
-    KP_HIP(ctx, hipMemcpyAsync(Y, sa.Y, nY * 8, hipMemcpyDeviceToHost, s));
-    if (nI) KP_HIP(ctx, hipMemcpyAsync(info, sa.info, nI * 8, hipMemcpyDeviceToHost, s));
-    KP_HIP(ctx, hipMemcpyAsync(steps_done, sa.steps_done, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s));
-    KP_HIP(ctx, hipMemcpyAsync(status, sa.status, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s));
-    KP_HIP(ctx, hipStreamSynchronize(s));
-  }
+  if (int rcd = kp_sim_download(ctx, io, S, U, Y, info, steps_done, status)) return rcd;
   float ms = 0;
   if (hipEventElapsedTime(&ms, ctx->evp[4], ctx->evp[5]) == hipSuccess) ctx->timers[21] = ms;
   return KP_OK;

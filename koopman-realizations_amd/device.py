@@ -794,6 +794,29 @@ def fit_refine(ctx: Context, basis: Basis, snaps: Snapshots, K, steps=1):
     return Kc
 
 
+def _sim_marshal(ctl, ref_sc, y0_sc, u0_sc, aux_w):
+    """The arguments that kp_mpc_simulate and kp_nmpc_simulate share, for the controller ctl (nproj, m): checks ref_sc and
+    u0_sc against y0_sc's trial count (the caller checks the width of y0_sc itself) and allocates the outputs; aux_w is the
+    width of the third output's rows (None: no such output).  Returns ((nb, nref, ref, shared, y0, u0), (U, Y, aux,
+    steps_done, status), the outputs' pointers): the first and last as the library takes them (the pointers keep their
+    arrays alive)."""
+    y0 = np.ascontiguousarray(np.atleast_2d(y0_sc), dtype=np.float64)
+    u0 = np.ascontiguousarray(np.atleast_2d(u0_sc), dtype=np.float64)
+    ref = np.ascontiguousarray(ref_sc, dtype=np.float64)
+    nb, n = y0.shape
+    shared = ref.ndim == 2
+    if ref.ndim not in (2, 3) or ref.shape[-1] != ctl.nproj or (not shared and ref.shape[0] != nb):
+        raise ValueError(f"ref_sc must be (nref, {ctl.nproj}) or ({nb}, nref, {ctl.nproj}), not {ref.shape}")
+    if u0.shape != (nb, ctl.m):
+        raise ValueError(f"u0_sc must be ({nb}, {ctl.m}), not {u0.shape}")
+    nref = ref.shape[-2]
+    U = np.zeros((nb, nref, ctl.m)); Y = np.zeros((nb, nref, n))
+    aux = None if aux_w is None else np.zeros((nb, max(nref - 1, 0), aux_w))
+    sd = np.zeros(nb, dtype=np.int32); st = np.zeros(nb, dtype=np.int32)
+    return ((nb, nref, F.dptr(ref), 1 if shared else 0, F.dptr(y0), F.dptr(u0)), (U, Y, aux, sd, st),
+            (F.dptr(U), F.dptr(Y), F.dptr(aux), sd.ctypes.data_as(F.c_ip), st.ctypes.data_as(F.c_ip)))
+
+
 class Mpc:
     """kp_mpc: condensed MPC problem of a linear / bilinear Koopman model on the device."""
 
@@ -893,26 +916,13 @@ class Mpc:
         units).  ref_sc: (nref, nproj) for every trial or (nb, nref, nproj); y0_sc (nb, n), u0_sc (nb, m).  Returns
         (U (nb, nref, m), Y (nb, nref, n), Z (nb, nref-1, N) or None, steps_done (nb,), status (nb,)); rows behind a failed
         step are NaN.  The kernel time is ctx.timer(F.TIMER_MPC_SIM) afterwards, ms."""
-        y0 = np.ascontiguousarray(np.atleast_2d(y0_sc), dtype=np.float64)
-        u0 = np.ascontiguousarray(np.atleast_2d(u0_sc), dtype=np.float64)
-        ref = np.ascontiguousarray(ref_sc, dtype=np.float64)
-        nb, n = y0.shape
-        shared = ref.ndim == 2
-        if ref.ndim not in (2, 3) or ref.shape[-1] != self.nproj or (not shared and ref.shape[0] != nb):
-            raise ValueError(f"ref_sc must be (nref, {self.nproj}) or ({nb}, nref, {self.nproj}), not {ref.shape}")
-        if u0.shape != (nb, self.m):
-            raise ValueError(f"u0_sc must be ({nb}, {self.m}), not {u0.shape}")
+        (nb, nref, *inputs), outs, ptrs = _sim_marshal(self, ref_sc, y0_sc, u0_sc, self.N if want_Z else None)
+        n = outs[1].shape[2]
         if n != basis.nzeta:       # the library reads nzeta outputs per row: a model with delays is not this loop
             raise F.KoopmanHipError(F.KP_ERR_ARG, f"kp_mpc_simulate: y0 has n = {n} entries, the dictionary's zeta has "
                                                   f"{basis.nzeta} (models with delays have no such loop)")
-        nref = ref.shape[-2]
-        U = np.zeros((nb, nref, self.m)); Y = np.zeros((nb, nref, n))
-        Z = np.zeros((nb, max(nref - 1, 0), self.N)) if want_Z else None
-        sd = np.zeros(nb, dtype=np.int32); st = np.zeros(nb, dtype=np.int32)
-        F.check(F.lib().kp_mpc_simulate(self._h, basis._h, nb, nref, F.dptr(ref), 1 if shared else 0, F.dptr(y0), F.dptr(u0),
-                                        int(iters), F.dptr(U), F.dptr(Y), F.dptr(Z), sd.ctypes.data_as(F.c_ip),
-                                        st.ctypes.data_as(F.c_ip)), self.ctx.handle)
-        return U, Y, Z, sd, st
+        F.check(F.lib().kp_mpc_simulate(self._h, basis._h, nb, nref, *inputs, int(iters), *ptrs), self.ctx.handle)
+        return outs
 
     def last_qp(self):
         """(Hq, f, Aq, bq) of the most recent single-problem step: quadprog(Hq, f, Aq, bq)."""
@@ -1014,25 +1024,12 @@ class Nmpc:
         step but the first starts from the previous step's solution, shifted.  Returns (U (nb, nref, m), Y (nb, nref, nzeta),
         info (nb, nref-1, 3): SQP iterations, KKT residual, status of every step (None without want_info), steps_done (nb,),
         status (nb,)); rows behind a failed step are NaN.  The kernel time is ctx.timer(F.TIMER_NMPC_SIM) afterwards, ms."""
-        y0 = np.ascontiguousarray(np.atleast_2d(y0_sc), dtype=np.float64)
-        u0 = np.ascontiguousarray(np.atleast_2d(u0_sc), dtype=np.float64)
-        ref = np.ascontiguousarray(ref_sc, dtype=np.float64)
-        nb = y0.shape[0]
-        shared = ref.ndim == 2
-        if ref.ndim not in (2, 3) or ref.shape[-1] != self.nproj or (not shared and ref.shape[0] != nb):
-            raise ValueError(f"ref_sc must be (nref, {self.nproj}) or ({nb}, nref, {self.nproj}), not {ref.shape}")
-        if y0.shape[1] != self.nzeta:
-            raise ValueError(f"y0_sc must be ({nb}, {self.nzeta}), not {y0.shape}")
-        if u0.shape != (nb, self.m):
-            raise ValueError(f"u0_sc must be ({nb}, {self.m}), not {u0.shape}")
-        nref = ref.shape[-2]
-        U = np.zeros((nb, nref, self.m)); Y = np.zeros((nb, nref, self.nzeta))
-        info = np.zeros((nb, max(nref - 1, 0), 3)) if want_info else None
-        sd = np.zeros(nb, dtype=np.int32); st = np.zeros(nb, dtype=np.int32)
-        F.check(F.lib().kp_nmpc_simulate(self._h, nb, nref, F.dptr(ref), 1 if shared else 0, F.dptr(y0), F.dptr(u0),
-                                         1 if warm else 0, F.dptr(U), F.dptr(Y), F.dptr(info), sd.ctypes.data_as(F.c_ip),
-                                         st.ctypes.data_as(F.c_ip)), self.ctx.handle)
-        return U, Y, info, sd, st
+        (nb, nref, *inputs), outs, ptrs = _sim_marshal(self, ref_sc, y0_sc, u0_sc, 3 if want_info else None)
+        n = outs[1].shape[2]
+        if n != self.nzeta:
+            raise ValueError(f"y0_sc must be ({nb}, {self.nzeta}), not {(nb, n)}")
+        F.check(F.lib().kp_nmpc_simulate(self._h, nb, nref, *inputs, 1 if warm else 0, *ptrs), self.ctx.handle)
+        return outs
 
     def last_jacobians(self):
         """[A_k B_k] = dF/d[zeta; u] at the Np points of the last linearisation of the last single step: (Np, nzeta, nvars)."""

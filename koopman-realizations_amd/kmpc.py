@@ -20,6 +20,7 @@ import time
 
 import numpy as np
 
+from . import _ffi as F
 from .device import Mpc, Nmpc
 
 
@@ -274,7 +275,9 @@ class Kmpc:
 
     # ---- Kmpc.m:403-512 ---------------------------------------------------------------------------
     def run_simulation(self, ref_y, y0=None, u0=None):
-        """Closed loop with the identified model as the plant (delays = 0)."""
+        """Closed loop with the identified model as the plant (delays = 0).  A nonlinear controller takes one SQP launch per
+        step (get_mpcInput_nonlinear) with the plant step F(zeta, u_{k-1}) on the host, and adds nmpc_info: (SQP iterations,
+        KKT residual, status) of every step, as Ksim does; its warm start (nmpc_warm_start) begins anew with every run."""
         p = self.params
         n, m = p["n"], p["m"]
         s = self.sysid
@@ -282,53 +285,37 @@ class Kmpc:
         u0 = np.zeros(m) if u0 is None else np.asarray(u0, dtype=np.float64)
         ref_sc = self.scaledown_ref(ref_y)
         res = {"T": [0.0], "U": [u0], "Y": [y0], "K": [0], "R": [np.atleast_2d(ref_y)[0]], "Z": [], "comp_time": []}
-        if self.model_type == "nonlinear":
-            return self._run_simulation_nonlinear(ref_sc, res)
-        k = 1
-        while k < ref_sc.shape[0]:
-            cur = {"y": s.scaledown_y(res["Y"][-1])[None, :], "u": s.scaledown_u(res["U"][-1])[None, :]}
-            refhor = ref_sc[k - 1:k + self.horizon]
-            t0 = time.perf_counter()
-            if self.model_type == "linear":
-                U, z = self.get_mpcInput(cur, refhor)
-            else:
-                U, z = self.get_mpcInput_bilinear_iter(cur, refhor, 1)
-            res["comp_time"].append(time.perf_counter() - t0)
-            if np.isnan(U).any():
-                break
-            u_k_sc = s.scaledown_u(res["U"][-1])                    # Kmpc.m:495 one-step input delay
-            if self.model_type == "linear":
-                z1 = self.model["A"] @ z + self.model["B"] @ u_k_sc
-            else:
-                z1 = self.model["A"] @ z + self.model["Beta"](z) @ u_k_sc
-            res["T"].append(k * p["Ts"]); res["U"].append(s.scaleup_u(U[1])); res["Y"].append(s.scaleup_y(self.model["C"] @ z1))
-            res["K"].append(k); res["R"].append(self.scaleup_ref(ref_sc[k - 1])[0]); res["Z"].append(z)
-            k += 1
-        return {k_: np.array(v) for k_, v in res.items()}
-
-    def _run_simulation_nonlinear(self, ref_sc, res):
-        """run_simulation's loop for a nonlinear model: one SQP launch per step (get_mpcInput_nonlinear), the plant step
-        F(zeta, u_{k-1}) on the host.  Adds nmpc_info: (SQP iterations, KKT residual, status) of every step, as Ksim does.
-        A warm start (nmpc_warm_start) begins anew with every run."""
-        p, s = self.params, self.sysid
-        self._U_last = None
-        res["nmpc_info"] = []
+        nonlinear = self.model_type == "nonlinear"
+        # the controller step (cur, reference window) -> (U, z) and the plant step (cur, z) -> scaled y_k, which sees
+        # u_{k-1}: the one-step input delay of Kmpc.m:495
+        if nonlinear:
+            self._U_last = None
+            res["nmpc_info"] = []
+            step = self.get_mpcInput_nonlinear
+            plant = lambda cur, z: self.model["F_func"](cur["y"][0], cur["u"][0])
+        elif self.model_type == "linear":
+            step = self.get_mpcInput
+            plant = lambda cur, z: self.model["C"] @ (self.model["A"] @ z + self.model["B"] @ cur["u"][0])
+        else:
+            step = self.get_mpcInput_bilinear
+            plant = lambda cur, z: self.model["C"] @ (self.model["A"] @ z + self.model["Beta"](z) @ cur["u"][0])
         k = 1
         while k < ref_sc.shape[0]:
             cur = {"y": s.scaledown_y(res["Y"][-1])[None, :], "u": s.scaledown_u(res["U"][-1])[None, :]}
             t0 = time.perf_counter()
-            U, z = self.get_mpcInput_nonlinear(cur, ref_sc[k - 1:k + self.horizon])
+            U, z = step(cur, ref_sc[k - 1:k + self.horizon])
             res["comp_time"].append(time.perf_counter() - t0)
-            res["nmpc_info"].append(self.last_info)
+            if nonlinear:
+                res["nmpc_info"].append(self.last_info)
             if np.isnan(U).any():
                 break
-            y1 = self.model["F_func"](cur["y"][0], cur["u"][0])          # Kmpc.m:495 one-step input delay
-            res["T"].append(k * p["Ts"]); res["U"].append(s.scaleup_u(U[1])); res["Y"].append(s.scaleup_y(y1))
+            res["T"].append(k * p["Ts"]); res["U"].append(s.scaleup_u(U[1])); res["Y"].append(s.scaleup_y(plant(cur, z)))
             res["K"].append(k); res["R"].append(self.scaleup_ref(ref_sc[k - 1])[0]); res["Z"].append(z)
             k += 1
         out = {k_: np.array(v) for k_, v in res.items()}
-        out["Z"] = out["Z"].reshape(-1, p["N"])
-        out["nmpc_info"] = out["nmpc_info"].reshape(-1, 3)
+        if nonlinear:
+            out["Z"] = out["Z"].reshape(-1, p["N"])
+            out["nmpc_info"] = out["nmpc_info"].reshape(-1, 3)
         return out
 
     # ---- Kmpc.m:390-399 ---------------------------------------------------------------------------
@@ -376,50 +363,46 @@ class Kmpc:
                 r["steps_done"] = len(r["K"]) - 1
                 out.append(r)
             return out
-        nref = ref_list[0].shape[0]
+        ref_sc = self._stack_refs(ref_list)
+        U, Y, Z, sd, st = self.dev.simulate(self.sysid.basis_dev, ref_sc, s.scaledown_y(y0s), s.scaledown_u(u0s), 1, True)
+        return self._trial_dicts(ref_list, ref_sc, y0s, u0s, U, Y, sd, F.TIMER_MPC_SIM, lambda i, k: Z[i, :k - 1].copy())
+
+    def _stack_refs(self, ref_list):
+        """The scaled-down references of a batched run: (nref, nproj) when one serves every trial, else (nb, nref, nproj)."""
         if any(r.shape != ref_list[0].shape for r in ref_list):
             raise ValueError("run_simulations: every reference must have the same number of rows")
-        ref_sc = self.scaledown_ref(ref_list[0]) if len(ref_list) == 1 else np.stack([self.scaledown_ref(r) for r in ref_list])
-        U, Y, Z, sd, st = self.dev.simulate(self.sysid.basis_dev, ref_sc, s.scaledown_y(y0s), s.scaledown_u(u0s), 1, True)
-        from . import _ffi as F
+        return self.scaledown_ref(ref_list[0]) if len(ref_list) == 1 else np.stack([self.scaledown_ref(r) for r in ref_list])
+
+    def _trial_dicts(self, ref_list, ref_sc, y0s, u0s, U, Y, sd, timer, Z_of, extra=None):
+        """run_simulation's dict for every trial of a batched run, scaled up and cut behind the last completed step.  timer:
+        the slot of the launch's kernel time; Z_of(i, k): trial i's Z rows; extra(i, k): fields that go before steps_done."""
+        p, s = self.params, self.sysid
         steps = int(sd.sum())
-        per_step = self.ctx.timer(F.TIMER_MPC_SIM) * 1e-3 / steps if steps else 0.0
+        per_step = self.ctx.timer(timer) * 1e-3 / steps if steps else 0.0
         out = []
-        for i in range(nb):
+        for i in range(len(sd)):
             k = int(sd[i]) + 1                                         # rows 0 .. steps_done
+            ref_i = ref_list[i if len(ref_list) > 1 else 0]
             rs = ref_sc if ref_sc.ndim == 2 else ref_sc[i]
-            R = np.vstack([ref_list[i if len(ref_list) > 1 else 0][:1], self.scaleup_ref(rs[:k - 1])]) if k > 1 else \
-                ref_list[i if len(ref_list) > 1 else 0][:1].copy()
+            R = np.vstack([ref_i[:1], self.scaleup_ref(rs[:k - 1])]) if k > 1 else ref_i[:1].copy()
             out.append({"T": np.arange(k) * p["Ts"], "U": np.vstack([u0s[i:i + 1], s.scaleup_u(U[i, 1:k])]),
-                        "Y": np.vstack([y0s[i:i + 1], s.scaleup_y(Y[i, 1:k])]), "K": np.arange(k), "R": R,
-                        "Z": Z[i, :k - 1].copy(), "comp_time": np.full(k - 1, per_step), "steps_done": int(sd[i])})
+                        "Y": np.vstack([y0s[i:i + 1], s.scaleup_y(Y[i, 1:k])]), "K": np.arange(k), "R": R, "Z": Z_of(i, k),
+                        "comp_time": np.full(k - 1, per_step), **(extra(i, k) if extra else {}), "steps_done": int(sd[i])})
         return out
 
     def _run_simulations_nonlinear(self, ref_list, y0s, u0s):
         """run_simulations for a nonlinear controller: every trial's loop in ONE launch (kp_nmpc_simulate), state bounds
         included; warm = nmpc_warm_start.  Each dict also holds nmpc_info, (SQP iterations, KKT residual, status) per step."""
-        from . import _ffi as F
-        p, s = self.params, self.sysid
-        nb = y0s.shape[0]
-        if any(r.shape != ref_list[0].shape for r in ref_list):
-            raise ValueError("run_simulations: every reference must have the same number of rows")
-        ref_sc = self.scaledown_ref(ref_list[0]) if len(ref_list) == 1 else np.stack([self.scaledown_ref(r) for r in ref_list])
+        s, N, n = self.sysid, self.params["N"], self.params["n"]
+        ref_sc = self._stack_refs(ref_list)
         U, Y, info, sd, st = self.dev.simulate(ref_sc, s.scaledown_y(y0s), s.scaledown_u(u0s), bool(self.nmpc_warm_start))
-        steps = int(sd.sum())
-        per_step = self.ctx.timer(F.TIMER_NMPC_SIM) * 1e-3 / steps if steps else 0.0
-        N, n = p["N"], p["n"]
-        out = []
-        for i in range(nb):
-            k = int(sd[i]) + 1                                         # rows 0 .. steps_done
-            ref_i = ref_list[i if len(ref_list) > 1 else 0]
-            rs = ref_sc if ref_sc.ndim == 2 else ref_sc[i]
-            R = np.vstack([ref_i[:1], self.scaleup_ref(rs[:k - 1])]) if k > 1 else ref_i[:1].copy()
+
+        def Z_of(i, k):                     # [zeta; 0] as get_mpcInput_nonlinear returns it (Kmpc.m:1180)
             Z = np.zeros((k - 1, N))
-            Z[:, :n] = Y[i, :k - 1]                                    # [zeta; 0] as get_mpcInput_nonlinear returns it (Kmpc.m:1180)
-            out.append({"T": np.arange(k) * p["Ts"], "U": np.vstack([u0s[i:i + 1], s.scaleup_u(U[i, 1:k])]),
-                        "Y": np.vstack([y0s[i:i + 1], s.scaleup_y(Y[i, 1:k])]), "K": np.arange(k), "R": R, "Z": Z,
-                        "comp_time": np.full(k - 1, per_step), "nmpc_info": info[i, :k - 1].copy(), "steps_done": int(sd[i])})
-        return out
+            Z[:, :n] = Y[i, :k - 1]
+            return Z
+        return self._trial_dicts(ref_list, ref_sc, y0s, u0s, U, Y, sd, F.TIMER_NMPC_SIM, Z_of,
+                                 lambda i, k: {"nmpc_info": info[i, :k - 1].copy()})
 
 
 class Ksim:

@@ -241,6 +241,44 @@ def test_more_trials_than_are_resident(ctx):
     assert not same_bits(Y[0], Y[1])
 
 
+SIM_PINNED_BYTES = 4 << 20      # up to here a call's results come back in one copy through page-locked scratch
+
+
+def sim_block_bytes(nb, nref, nproj, ny, m, aux_w, shared):
+    """The device block of one kp_mpc_simulate / kp_nmpc_simulate call (kp_sim_loop.h):
+    [ref | y0 | u0] | U | Y | aux | steps_done, status - doubles, the 2 nb ints rounded up to whole doubles."""
+    n_in = (1 if shared else nb) * nref * nproj + nb * ny + nb * m
+    n_out = nb * nref * m + nb * nref * ny + nb * (nref - 1) * aux_w + (2 * nb + 1) // 2
+    return 8 * (n_in + n_out)
+
+
+def copies_of(big, one, rows):
+    """Every row of `big` listed in `rows` has the bits of one[0]."""
+    return big[rows].tobytes() == np.broadcast_to(one[:1], big[rows].shape).tobytes()
+
+
+def test_results_copied_straight_to_the_callers_arrays(ctx):
+    """A call above SIM_PINNED_BYTES copies each output straight into the caller's array; every trial of it has the bits of
+    the same start run alone, which comes back through the page-locked scratch."""
+    dic, s = synth_case(2, 2, 2, 7, "bilinear", 2)
+    mpc, b = make_mpc(ctx, s), make_basis(ctx, dic)
+    nref, nd = 6, 10
+    size = lambda nb: sim_block_bytes(nb, nref, 2, 2, 2, dic.N, True)
+    nb = nd * (SIM_PINNED_BYTES // (size(nd) - size(0)) + 1)
+    assert size(nb) > SIM_PINNED_BYTES >= size(nb - 2 * nd) and size(1) <= SIM_PINNED_BYTES, (nb, size(nb))
+    ref, y0, u0 = synth_inputs(s, nd, nref, seed=9)
+    idx = np.arange(nb) % nd
+    U, Y, Z, sd, st = mpc.simulate(b, ref[0], y0[idx], u0[idx])
+    assert (st == F.KP_OK).all() and (sd == nref - 1).all()
+    for j in range(nd):
+        U1, Y1, Z1, sd1, st1 = mpc.simulate(b, ref[0], y0[j:j + 1], u0[j:j + 1])
+        rows = np.nonzero(idx == j)[0]
+        assert len(rows) == nb // nd
+        assert copies_of(U, U1, rows) and copies_of(Y, Y1, rows) and copies_of(Z, Z1, rows), j
+        assert copies_of(sd, sd1, rows) and copies_of(st, st1, rows), j
+    assert not same_bits(Y[0], Y[1])
+
+
 # ---- edges -------------------------------------------------------------------------------------------------------------
 def test_short_references(arm_cases):
     dic, s, mpc, b = arm_cases["bilinear"]

@@ -25,6 +25,7 @@ import koopman_realizations_amd as kra
 from koopman_realizations_amd import _ffi as F
 from oracle import koopman_oracle as ko
 from test_gpu_fit import make_basis
+from test_gpu_mpc_sim import SIM_PINNED_BYTES, copies_of, sim_block_bytes
 from test_gpu_nmpc import arm_ks, arm_nl, arm_nmpc, arm_setup, example_kmpc, synth  # noqa: F401  (fixtures among them)
 from test_nmpc_host import load_nmpc_golden
 
@@ -222,6 +223,28 @@ def test_more_trials_than_are_resident(ctx):
         assert len(rows) == 30
         assert all(same_bits(U[i], U1[0]) and same_bits(Y[i], Y1[0]) and same_bits(info[i], i1[0]) and st[i] == st1[0]
                    for i in rows), j
+    assert not same_bits(Y[0], Y[1])
+
+
+def test_results_copied_straight_to_the_callers_arrays(ctx):
+    """A call above SIM_PINNED_BYTES copies each output straight into the caller's array; every trial of it has the bits of
+    the same start run alone, which comes back through the page-locked scratch."""
+    c = small_model(ctx, *SMALL[0])
+    dev, rng = c["dev"], c["rng"]
+    nref, nd = 5, 10
+    size = lambda nb: sim_block_bytes(nb, nref, 1, 2, 1, 3, True)
+    nb = nd * (SIM_PINNED_BYTES // (size(nd) - size(0)) + 1)
+    assert size(nb) > SIM_PINNED_BYTES >= size(nb - 2 * nd) and size(1) <= SIM_PINNED_BYTES, (nb, size(nb))
+    y0 = rng.uniform(-0.5, 0.5, (nd, 2)); u0 = rng.uniform(-0.3, 0.3, (nd, 1))
+    idx = np.arange(nb) % nd
+    U, Y, info, sd, st = dev.simulate(c["ref"][:nref], y0[idx], u0[idx])
+    assert (st != F.KP_ERR_QP_FAIL).all() and (sd == nref - 1).all()
+    for j in range(nd):
+        U1, Y1, i1, sd1, st1 = dev.simulate(c["ref"][:nref], y0[j:j + 1], u0[j:j + 1])
+        rows = np.nonzero(idx == j)[0]
+        assert len(rows) == nb // nd
+        assert copies_of(U, U1, rows) and copies_of(Y, Y1, rows) and copies_of(info, i1, rows), j
+        assert copies_of(sd, sd1, rows) and copies_of(st, st1, rows), j
     assert not same_bits(Y[0], Y[1])
 
 
