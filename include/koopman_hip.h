@@ -103,7 +103,9 @@ int kp_device_info(const kp_ctx* ctx, char* name, int name_len, int* num_cu, int
  * order 0 everywhere for A/B runs and tests.  21: the kernel of the most recent batch of nonlinear closed loops (kp_nmpc_simulate,
  * koopman_hip_nmpc.h), ms.  22: the kernel of the most recent batched eigensolver call (kp_eig, koopman_hip_spectrum.h), ms.  23: not
  * a time - the regime that call ran: 1 a wave per matrix, 2 a workgroup with the matrix in LDS, 3 a workgroup with the matrix in a
- * workspace slot; environment variable KP_EIG_REGIME (read per call) forces 2 or 3 for A/B runs and tests. */
+ * workspace slot; environment variable KP_EIG_REGIME (read per call) forces 2 or 3 for A/B runs and tests.  24: the two kernels of
+ * the most recent prediction-horizon validation (kp_validate_horizon, koopman_hip_horizon.h), ms.  25: not a time - 1000 x (its model
+ * rows were staged in LDS) + the tile width S_T it ran, 64, 32 or 16 starts. */
 int kp_timer_get(const kp_ctx* ctx, int which, double* ms);
 /* Device pointer + byte size of the library stream's raw handle, for profilers/benchmarks
  * that want to bracket work with their own HIP events: returns hipStream_t as void*. */

@@ -75,4 +75,7 @@ int kp_validate_ct(kp_ctx* ctx, const kp_basis* basis, int model_type, int N, in
 #ifdef __cplusplus
 }
 #endif
+
+/* prediction-horizon validation, the h-step-ahead errors from every start sample (kp_validate_horizon): its own header */
+#include "koopman_hip_horizon.h"
 #endif /* KOOPMAN_HIP_VALIDATE_H */

@@ -1,12 +1,15 @@
 """Command line: identify a Koopman model from a reference data file, without MATLAB.
 
     python -m koopman_realizations_amd sysid DATA.mat --model_type bilinear --obs_degree 3 [--dim_red]
-        [--time_type continuous] [--lasso 1 10 100 --metric euclid_mean] [--spectrum] [--out model.npz]
+        [--time_type continuous] [--lasso 1 10 100 --metric euclid_mean [--horizon 10 [--horizon_stride 1]]] [--spectrum]
+        [--out model.npz]
 
 is example_sysid.m:22-65 (Ksysid constructor, train_models, validation of every `val` trial) with the options of
 Ksysid_setup.m; prints the validation errors and optionally stores the model matrices.  With several --lasso values every
 candidate is validated on every trial (one device call, Ksysid.val_candidates), the candidate with the least --metric is
-chosen (Ksysid.select_model) and that one is reported and stored.  --spectrum prints the spectral radius, stability and the
+chosen (Ksysid.select_model) and that one is reported and stored.  With --horizon H the choice is made by the error of the
+H-th prediction step from every start sample of every trial instead (one device call, Ksysid.val_horizon), printed per
+candidate.  --spectrum prints the spectral radius, stability and the
 five leading eigenvalues of every candidate (one device call, Ksysid.candidate_spectra) and stores the chosen model's
 eigenvalues with --out."""
 from __future__ import annotations
@@ -29,6 +32,9 @@ def main(argv=None):
     s.add_argument("--lasso", nargs="+", type=float, default=[float("inf")])
     s.add_argument("--metric", default="euclid_mean", choices=["mean", "rmse", "nrmse", "euclid_mean", "unscaled_euclid_mean"],
                    help="with several --lasso values: the validation error, averaged over the trials, that picks the model")
+    s.add_argument("--horizon", type=int, default=None,
+                   help="choose by the --metric of the H-th prediction step from every start sample (the horizon an MPC uses), not by whole-trial rollouts")
+    s.add_argument("--horizon_stride", type=int, default=1, help="with --horizon: every how many samples a prediction starts")
     s.add_argument("--delays", type=int, default=0)
     s.add_argument("--dim_red", action="store_true")
     s.add_argument("--loaded", action="store_true")
@@ -39,6 +45,8 @@ def main(argv=None):
                    help="print radius, stability and the five leading eigenvalues of every candidate (linear / bilinear models)")
     s.add_argument("--out", default=None, help="write the model (A, B, C, K, scale) to this .npz")
     a = ap.parse_args(argv)
+    if a.horizon is not None and a.metric == "nrmse":
+        ap.error("--metric nrmse is not defined with --horizon")
 
     from . import Context, Ksysid          # needs libkoopman_hip.so and a GPU: fails loudly otherwise
     from .matio import load_data4sysid
@@ -62,10 +70,21 @@ def main(argv=None):
         for c, lv in enumerate(tab["lasso"]):
             print(f"candidate {c}: lasso {lv:g}" + ("  (diverged)" if tab["diverged"][c].any() else ""))
             lines(c, "  ")
-        best, _ = ks.select_model(a.metric, tab)
-        print(f"chosen by {a.metric}: candidate {best} (lasso {tab['lasso'][best]:g})")
+        if a.horizon is None:
+            best, _ = ks.select_model(a.metric, tab)
+            print(f"chosen by {a.metric}: candidate {best} (lasso {tab['lasso'][best]:g})")
+        else:
+            sl = ks.horizon_slice(ks.val_horizon(a.horizon, stride=a.horizon_stride), a.horizon)
+            for c, lv in enumerate(sl["lasso"]):
+                print(f"horizon {a.horizon}: candidate {c}: lasso {lv:g}  {a.metric} {sl[a.metric][c].mean():.6g}"
+                      + ("  (diverged)" if sl["diverged"][c].any() else ""))
+            best, _ = ks.select_model(a.metric, sl, horizon=a.horizon)
+            print(f"chosen by {a.metric} at step {a.horizon}: candidate {best} (lasso {sl['lasso'][best]:g})")
     else:
         lines(0, "")
+        if a.horizon is not None:
+            sl = ks.horizon_slice(ks.val_horizon(a.horizon, stride=a.horizon_stride), a.horizon)
+            print(f"horizon {a.horizon}: candidate 0:  {a.metric} {sl[a.metric][0].mean():.6g}" + ("  (diverged)" if sl["diverged"][0].any() else ""))
     extra = {}
     if a.spectrum and (a.model_type == "nonlinear" or a.loaded):
         print("--spectrum: not available for nonlinear or loaded models (Ksysid.spectrum covers linear and bilinear ones)")

@@ -187,6 +187,14 @@ VALIDATE_SIGNATURES = {
                                  C.POINTER(C.c_int64), c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int, C.c_double, C.c_double, C.c_double,
                                  c_dp, c_ip, c_dp, c_ip, c_ip]),
 }
+# prediction-horizon validation (include/koopman_hip_horizon.h)
+HORIZON_SIGNATURES = {
+    "kp_validate_horizon": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_dp, c_dp, C.c_int,
+                                      C.POINTER(C.c_int64), c_dp, c_dp, c_dp, C.c_int, C.c_int, c_dp, C.POINTER(C.c_int64), c_ip]),
+}
+TIMER_HORIZON = 24                 # kp_timer_get slot: the two kernels of the most recent kp_validate_horizon, ms
+TIMER_HORIZON_TILE = 25            # ... and 1000 x (model rows staged in LDS) + the tile width S_T it ran (64, 32 or 16)
+HORIZON_CHUNK = 8                  # KP_HORIZON_CHUNK
 VALIDATE_CHUNK = 128               # KP_VALIDATE_CHUNK
 VALIDATE_CT_CHUNK = 32             # KP_VALIDATE_CT_CHUNK
 VALIDATE_CT_STAGE = 8192           # KP_VALIDATE_CT_STAGE
@@ -219,7 +227,7 @@ def lib():
                           "(make -C koopman-realizations_amd/csrc)")
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in (SIGNATURES | NMPC_SIGNATURES | OBSERVER_SIGNATURES | CT_SIGNATURES | ARM_SIGNATURES
-                                   | RSYS_SIGNATURES | VALIDATE_SIGNATURES | SIM_SIGNATURES | SPECTRUM_SIGNATURES).items():
+                                   | RSYS_SIGNATURES | VALIDATE_SIGNATURES | HORIZON_SIGNATURES | SIM_SIGNATURES | SPECTRUM_SIGNATURES).items():
             fn = getattr(l, name)
             fn.restype, fn.argtypes = res, args
         _lib = l

@@ -1,4 +1,5 @@
-// The argument checks that kp_validate (kp_validate.hip) and kp_validate_ct (kp_validate_ct.hip) share.
+// The argument checks that kp_validate (kp_validate.hip), kp_validate_ct (kp_validate_ct.hip) and kp_validate_horizon
+// (kp_validate_horizon.hip) share.
 #pragma once
 #include <string>
 
@@ -35,5 +36,17 @@ inline int val_check_args(kp_ctx* ctx, const std::string& fn, const kp_basis* ba
     if (Tq > INT32_MAX) return ctx->fail(KP_ERR_ARG, fn + ": trial " + std::to_string(q) + " is too long");
   }
   if ((int64_t)nmod * ntr > INT32_MAX) return ctx->fail(KP_ERR_ARG, fn + ": too many (model, trial) pairs");
+  return KP_OK;
+}
+
+// What kp_validate_horizon (kp_validate_horizon.hip) checks beyond val_check_args, which it calls with its Zeta as zeta0 and
+// Yreal: the real outputs are the first n columns of Zeta.
+inline int val_check_horizon_args(kp_ctx* ctx, const std::string& fn, int n, int nzeta, int H, int stride, const int64_t* nstart_out) {
+  if (!nstart_out) return ctx->fail(KP_ERR_ARG, fn + ": bad argument");
+  if (H < 1 || stride < 1)
+    return ctx->fail(KP_ERR_ARG, fn + ": the horizon H = " + std::to_string(H) + " and the stride = " + std::to_string(stride) +
+                                     " must be at least 1");
+  if (n > nzeta)
+    return ctx->fail(KP_ERR_ARG, fn + ": n = " + std::to_string(n) + " outputs, but Zeta has " + std::to_string(nzeta) + " columns");
   return KP_OK;
 }

@@ -470,6 +470,28 @@ class Context:
             sim = [[np.ascontiguousarray(S[i, :, off[q]:off[q + 1]].T) for q in range(ntr)] for i in range(nmod)]
         return err, st, sim
 
+    def validate_horizon(self, basis, model_type, models, trials, n, yfactor, horizon, stride=1):
+        """kp_validate_horizon: the h-step-ahead prediction errors, h = 1 .. horizon, of every model from every start sample
+        of every trial, one device call.  basis: the unloaded dictionary; models as `validate` takes them (nw = 0); trials: a
+        list of (Zeta (T x nzeta), U (T x m)), the delay-embedded states and inputs after the nd shift - the first n columns
+        of Zeta are the real outputs; starts s = 0, stride, ... while s + horizon <= T - 1.  Returns (err (nmod, ntr, horizon,
+        2 n + 2): [mean |d| | rmse | euclid_mean | unscaled euclid_mean] over the starts of the trial, NaN for a trial without
+        a start; starts (ntr); status (nmod, ntr): 1 where a prediction left the finite range)."""
+        N, m, nz, n = basis.N, basis.m, basis.nzeta, int(n)
+        nmod, ntr, H = len(models), len(trials), int(horizon)
+        Zs = [np.asarray(z, dtype=np.float64).reshape(-1, nz) for z, _ in trials]
+        packed = [(z[0] if z.shape[0] else np.zeros(nz), u, z[:, :min(n, nz)], None) for z, (_, u) in zip(Zs, trials)]
+        A, B, off, _, U, _, _ = self._validate_pack(basis, model_type, models, packed, min(n, nz), 0)
+        Z = F.fcol(np.vstack(Zs))
+        fac = np.ascontiguousarray(np.broadcast_to(np.asarray(yfactor, dtype=np.float64), (n,)))
+        err = np.zeros((nmod, ntr, max(H, 0), 2 * n + 2)); st = np.zeros((nmod, ntr), dtype=np.int32)
+        ns = np.zeros(ntr, dtype=np.int64)
+        F.check(F.lib().kp_validate_horizon(self._h, basis.handle, F.MODEL[model_type], N, m, n, nz, nmod, F.dptr(A), F.dptr(B), ntr,
+                                            off.ctypes.data_as(C.POINTER(C.c_int64)), F.dptr(Z), F.dptr(U), F.dptr(fac), H,
+                                            int(stride), F.dptr(err), ns.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            st.ctypes.data_as(F.c_ip)), self._h)
+        return err, ns, st
+
     def validate_ct(self, basis, model_type, models, trials, n, yfactor, Ts, rtol=1e-3, atol=1e-6, want_sim=False, nw=0):
         """kp_validate_ct: `validate` for continuous-time models - every sample interval of every (model, trial) pair is ode45
         over [0, Ts] with the input held (the step control of rollout_ct / rollout_nl_ct), one launch for the whole table.

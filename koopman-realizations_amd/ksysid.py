@@ -896,15 +896,99 @@ class Ksysid:
         return results, errs
 
     _TABLE_METRICS = ("mean", "rmse", "nrmse", "euclid_mean", "unscaled_euclid_mean")
+    _HORIZON_METRICS = ("mean", "rmse", "euclid_mean", "unscaled_euclid_mean")
 
-    def select_model(self, metric="euclid_mean", table=None, require_stable=False):
+    # ---- prediction-horizon validation: h-step-ahead errors from every start sample (kp_validate_horizon) ------------
+    def val_horizon(self, horizon, models=None, valdata=None, stride=1):
+        """The h-step-ahead prediction errors, h = 1 .. horizon, of every candidate from every start sample of every validation
+        trial, in ONE device call (kp_validate_horizon) - the error a receding-horizon controller sees, where val_candidates
+        rolls each trial once from its first row.  Trial q (T_q rows after the nd shift) is started at s = 0, stride, 2 stride,
+        ... while s + horizon <= T_q - 1; the prediction of step h from start s is compared with the real output of row s + h,
+        and every h is averaged over the same starts.  models, valdata: as val_candidates takes them.  Returns a dict: mean,
+        rmse (nmod, ntr, H, n), euclid_mean, unscaled_euclid_mean (nmod, ntr, H) - NaN for a trial too short for one start -,
+        starts (ntr), diverged (nmod, ntr; bool: a prediction left the finite range), horizon, stride, lasso (nmod) when every
+        model carries it, and pooled: the same four metrics over all starts of all trials together ((nmod, H, n) and (nmod, H):
+        means weighted by the trials' starts, rmse from the pooled squares).  There is no nrmse: its normaliser is a property
+        of a whole trial.  Continuous-time and loaded models are not covered."""
+        if self.time_type == "continuous":
+            raise NotImplementedError("val_horizon: continuous-time models are not covered (the horizon steps are discrete-time recursions)")
+        if self.loaded:
+            raise NotImplementedError("val_horizon: loaded models are not covered (the load weights change per step and start)")
+        if models is None:
+            models = self.candidates if self.candidates is not None else self.model
+        if models is None:
+            raise ValueError("no model: call train_models first")
+        models = [models] if isinstance(models, dict) else list(models)
+        if valdata is None:
+            valdata = self.valdata
+        trials = [valdata] if isinstance(valdata, dict) else list(valdata)
+        if not models or not trials:
+            raise ValueError("val_horizon needs at least one model and one trial")
+        p = self.params; n = p["n"]
+        packed = []
+        for v in trials:
+            _, _, ureal, zetareal = self._val_common(v)
+            packed.append((zetareal, ureal))
+        mods = [mo["Kf"] for mo in models] if self.model_type == "nonlinear" else [(mo["A"], mo["B"]) for mo in models]
+        err, starts, st = self.ctx.validate_horizon(self.basis_dev, self.model_type, mods, packed, n, p["scale"]["y_factor"],
+                                                    horizon, stride)
+        tab = {"mean": err[..., :n].copy(), "rmse": err[..., n:2 * n].copy(), "euclid_mean": err[..., 2 * n].copy(),
+               "unscaled_euclid_mean": err[..., 2 * n + 1].copy(), "starts": starts, "diverged": st != 0,
+               "horizon": int(horizon), "stride": int(stride)}
+        if all("lasso" in mo for mo in models):
+            tab["lasso"] = np.array([float(mo["lasso"]) for mo in models])
+        tab["pooled"] = self._horizon_pool(tab)
+        return tab
+
+    @classmethod
+    def _horizon_pool(cls, tab):
+        """The four metrics over all starts of all trials together."""
+        w = np.asarray(tab["starts"], dtype=np.float64)
+        tot = w.sum()
+        keep = w > 0
+        out = {}
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            for k in cls._HORIZON_METRICS:
+                x = np.asarray(tab[k], dtype=np.float64)[:, keep]
+                wk = w[keep].reshape((1, -1) + (1,) * (x.ndim - 2))
+                if k == "rmse":
+                    out[k] = np.sqrt((wk * x ** 2).sum(axis=1) / tot) if tot > 0 else np.full(x.shape[:1] + x.shape[2:], np.nan)
+                else:
+                    out[k] = (wk * x).sum(axis=1) / tot if tot > 0 else np.full(x.shape[:1] + x.shape[2:], np.nan)
+        return out
+
+    @classmethod
+    def horizon_slice(cls, table, h):
+        """Step h (1-based) of a val_horizon table in the shape of a val_candidates one - mean, rmse (nmod, ntr', n),
+        euclid_mean, unscaled_euclid_mean, diverged (nmod, ntr') and lasso when the table has it -, which select_model takes
+        as `table`.  Trials without a start are left out; ValueError when none is left or h is outside 1 .. horizon."""
+        H = int(table["horizon"])
+        if int(h) != h or not 1 <= int(h) <= H:
+            raise ValueError(f"h must be a step of the table's horizon, 1 .. {H}")
+        keep = np.asarray(table["starts"]) > 0
+        if not keep.any():
+            raise ValueError("no validation trial is long enough for one start at this horizon")
+        out = {k: np.asarray(table[k])[:, keep, int(h) - 1].copy() for k in cls._HORIZON_METRICS}
+        out["diverged"] = np.asarray(table["diverged"], dtype=bool)[:, keep].copy()
+        if "lasso" in table:
+            out["lasso"] = np.asarray(table["lasso"]).copy()
+        return out
+
+    def select_model(self, metric="euclid_mean", table=None, require_stable=False, horizon=None, stride=1):
         """The choice the reference leaves to the user (Ksysid.m:1384-1386): the candidate whose `metric`, averaged over the
         validation trials (and the outputs, for mean / rmse / nrmse), is least.  Candidates that diverged on a trial, or
         whose average is NaN, rank last.  table: a val_candidates result (default: computed now).  Sets self.model and
         returns (index, table); ValueError when no candidate stays finite.  require_stable: candidates whose spectrum is not
-        stable (candidate_spectra: one device call; a "stable" entry of the table is taken instead) rank last as well."""
+        stable (candidate_spectra: one device call; a "stable" entry of the table is taken instead) rank last as well.
+        horizon: rank by the error of the horizon-th prediction step from every start sample instead (a missing table is
+        horizon_slice(val_horizon(horizon, stride=stride), horizon)); nrmse does not exist there."""
         if metric not in self._TABLE_METRICS:
             raise ValueError(f"metric must be one of {self._TABLE_METRICS}")
+        if horizon is not None:
+            if metric == "nrmse":
+                raise ValueError("nrmse is not defined at a prediction horizon: its normaliser is a property of a whole trial")
+            if table is None:
+                table = self.horizon_slice(self.val_horizon(horizon, stride=stride), horizon)
         if table is None:
             table = self.val_candidates()
         cands = self.candidates if self.candidates is not None else self.model
