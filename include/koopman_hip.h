@@ -105,7 +105,11 @@ int kp_device_info(const kp_ctx* ctx, char* name, int name_len, int* num_cu, int
  * a time - the regime that call ran: 1 a wave per matrix, 2 a workgroup with the matrix in LDS, 3 a workgroup with the matrix in a
  * workspace slot; environment variable KP_EIG_REGIME (read per call) forces 2 or 3 for A/B runs and tests.  24: the two kernels of
  * the most recent prediction-horizon validation (kp_validate_horizon, koopman_hip_horizon.h), ms.  25: not a time - 1000 x (its model
- * rows were staged in LDS) + the tile width S_T it ran, 64, 32 or 16 starts. */
+ * rows were staged in LDS) + the tile width S_T it ran, 64, 32 or 16 starts.  26: not a time - where the tiles of the most recent
+ * Kronecker Gram launch had their workgroup barrier: 1 in front of the tile's last quad steps, whose MFMAs then run over the
+ * latency of the next tile's first operand reads (the in-kernel-lift monomial form where timer 20 reads 1, with 4 to 6 quads per
+ * wave; with 6 quads and three inputs only a plan without jobs of two A groups, timer 15 = 0), 0 behind the last step.  The results do not depend on it, bit for bit; environment variable
+ * KP_GRAM3_EARLY_BARRIER=0 (read once) keeps placement 0 everywhere for A/B runs and tests. */
 int kp_timer_get(const kp_ctx* ctx, int which, double* ms);
 /* Device pointer + byte size of the library stream's raw handle, for profilers/benchmarks
  * that want to bracket work with their own HIP events: returns hipStream_t as void*. */

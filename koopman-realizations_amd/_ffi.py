@@ -194,7 +194,8 @@ HORIZON_SIGNATURES = {
 }
 TIMER_HORIZON = 24                 # kp_timer_get slot: the two kernels of the most recent kp_validate_horizon, ms
 TIMER_HORIZON_TILE = 25            # ... and 1000 x (model rows staged in LDS) + the tile width S_T it ran (64, 32 or 16)
-HORIZON_CHUNK = 8                  # KP_HORIZON_CHUNK
+TIMER_GRAM3_EARLY_BARRIER = 26     # where the tiles of the last Kronecker Gram launch had their barrier: 1 in front of the last quad steps, 0 behind the last
+HORIZON_CHUNK = 8                 # KP_HORIZON_CHUNK
 VALIDATE_CHUNK = 128               # KP_VALIDATE_CHUNK
 VALIDATE_CT_CHUNK = 32             # KP_VALIDATE_CT_CHUNK
 VALIDATE_CT_STAGE = 8192           # KP_VALIDATE_CT_STAGE

@@ -42,6 +42,9 @@
 // before), behind the tile's raw load in the vmcnt order: 0.3068 -> 0.3127 ms.  Kept since DESIGN 6.7 (LO below): with the lift's
 // LDS byte addresses formed once and passed through an empty asm at the top of the tile body no tile loop holds a scratch
 // access and the loop is 5.5 vector instructions per wave and tile shorter: 0.2884 -> 0.2844 ms of kernel per fit.
+// DESIGN 6.8 (EB below): the tile's barrier in front of its last two quad steps, the next tile's first operands requested right
+// behind it - every wave's operand pipeline used to drain at the barrier and refill in front of five weight multiplies; the
+// same instructions and bits.
 //
 // Replaces the per-row lift loop of Ksysid.get_Koopman (Ksysid.m:1030-1065) and the products
 // PxTPx, PxTPy (Ksysid.m:1114,1125) for model_type 'bilinear'.
@@ -93,6 +96,39 @@
 // `const`: a pointer that may be this or a kernel argument must stay a GLOBAL pointer (constant address space: flat loads)
 __device__ double kp_gram3_ones[KT3] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
 
+// EB (the early tile barrier of kp_gram3_kernel): where a tile of NQ quads per wave places its barrier and how it
+// times the lift's three chunks.  One function for the kernel and for the launcher, so that the timer slot tells what ran.
+#ifndef KP_GRAM3_EB_BEHIND
+#define KP_GRAM3_EB_BEHIND 0        // quad steps of a tile that run behind its barrier; 0: as many as B operands are requested ahead
+#endif
+struct Gram3TileTiming {
+  int pf;        // B operands are requested this many quad steps ahead
+  int sp, lag;   // lift chunk i: table reads at step i sp, multiplies and stores at step i sp + lag
+  int bs;        // step whose end holds the tile's barrier; -1: the barrier stays behind the last step (today's placement)
+};
+constexpr Gram3TileTiming gram3_tile_timing(int nq, bool lo, bool eb) {
+  const int nstep = (KT3 / 4) * nq, nch = 3;
+  const int pf_ahead = lo ? 2 : 3;                      // (2 and 4 steps ahead measured the same; LO: four registers for the lift's addresses)
+  const int pf = nstep < pf_ahead ? nstep : pf_ahead;
+  const int sp = nstep / nch > 0 ? nstep / nch : 1;
+  const int lag = sp / 2 > 0 ? sp / 2 : 1;
+  // (with the ordered lift only: the order e = tid + 256 j requests B operands three steps ahead and does not pin its twelve
+  // lift addresses - with operands carried across the tile boundary its NQ = 6 loops hold 14 to 16 scratch accesses each)
+  if (eb && lo) {
+    // the barrier step: every operand read of the tile is issued at or before it (B operands run pf steps ahead) unless fewer
+    // steps are asked to stay behind it; it must lie in the tile's last k-step (the A fragments and weights of every k-step are
+    // requested by then) and at or behind the last lift store.  The chunks move together - the largest spacing of at least
+    // two steps that fits, the lag kept - and where none fits the placement is today's: a compile-time matter, never a hazard.
+    const int behind = KP_GRAM3_EB_BEHIND > 0 && KP_GRAM3_EB_BEHIND < pf ? KP_GRAM3_EB_BEHIND : pf;
+    const int bs = nstep - 1 - behind;
+    for (int s = sp; s >= 2; --s) {
+      const int l = lag < s ? lag : s;
+      if (bs >= (KT3 / 4 - 1) * nq && (nch - 1) * s + l <= bs) return {pf, s, l, bs};
+    }
+  }
+  return {pf, sp, lag, -1};
+}
+
 // PCS: econ lift through a projection matrix (dim_red dictionaries)
 // EXT: fourier (def_fourierLift, Ksysid.m:694-731) and gaussian (def_gaussianLift, :790-817) blocks through the same table
 // TUP (round 6; m = 3 and m = 2: an even number of weights): the four blocks of a weighted A operand carry TWO weights - tuple p = (w_2p, w_2p, w_2p+1, w_2p+1) -
@@ -105,9 +141,16 @@ __device__ double kp_gram3_ones[KT3] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
 // LO (the same form, its default weight form; kp_gram3_lift.h): the lift's jobs sit in the slots of a table built on the host - every job of three
 // real factors in lift step 0, real factors first - so that lift steps 1 and 2 read two table entries and multiply once: 4
 // v_mul_f64 and 2 ds_read_b128 less per wave and tile, the same bits (a dropped factor is exactly 1.0).
-template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool TUP = false, bool P3 = false, bool LO = false>
+// EB (the same form, every weight form and plan): the tile's barrier sits at the end of quad step NSTEP - 1 - PF, not
+// behind the last one, the lift's chunks finish in front of it, and the operand reads that found nothing left to request (the
+// last PF steps' B operands, the last k-step's A fragment and weights) request the NEXT tile's first operands from the other
+// Psi buffer: the tile's last PF steps of MFMAs run from registers over that latency, and the next tile opens with its
+// operands present instead of a drained pipeline behind a barrier.  The same instructions, the same accumulation order.
+// gram3_tile_timing says which tiles take it (the ordered lift LO with NQ = 4, 5, 6); the others keep today's tile.
+template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool TUP = false, bool P3 = false, bool LO = false, bool EB = false>
 __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
   constexpr int NWT = (BM + 1) * (BM + 2) / 2;
+  static_assert(!EB || (!PCS && !EXT && !PRE), "early tile barrier: the in-kernel-lift monomial form");
   static_assert(!P3 || (!PCS && !EXT && !PRE), "three-entry table: the in-kernel-lift monomial form");
   static_assert(!LO || (!PCS && !EXT && !PRE), "ordered lift slots: the in-kernel-lift monomial form");
   static_assert(!TUP || NWT % 2 == 0, "paired weights: an even number of weights (m = 3: 10 = 5 tuples, m = 2: 6 = 3 tuples)");
@@ -595,10 +638,67 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
   }
 
   constexpr int NSTEP = (KT3 / 4) * NQ;                 // quad steps (NWT MFMAs each) per snapshot tile
-  constexpr int SP = NSTEP / NCH > 0 ? NSTEP / NCH : 1;
-  constexpr int LAG = SP / 2 > 0 ? SP / 2 : 1;
-  constexpr int PF_AHEAD = LO ? 2 : 3;                  // (2 and 4 steps ahead measured the same; LO: four registers for the lift's addresses)
-  constexpr int PF = NSTEP < PF_AHEAD ? NSTEP : PF_AHEAD;   // B operands requested this many quad steps ahead
+  constexpr Gram3TileTiming TT = gram3_tile_timing(NQ, LO, EB);
+  constexpr int SP = TT.sp;
+  constexpr int LAG = TT.lag;
+  constexpr int PF = TT.pf;                             // B operands requested this many quad steps ahead
+  // EBT: this instantiation places the tile's barrier at the end of step BS (EB, and the lift's chunks fit in front of it).
+  //
+  // Why that is free of races (tile t on Psi buffer CUR, the other one NXT; pow[] the two power tables):
+  //  * Reads of the current buffer.  Every LDS read of Psi[CUR] by tile t - B operands (PF steps ahead, so the last at step
+  //    NSTEP - 1 - PF <= BS, or held back to behind the barrier where fewer steps stay behind it), A fragments (first step of
+  //    the k-step before), weights (last step of the k-step before; the second A group's re-read never later than BS) - is
+  //    issued at or before step BS and retired by the s_waitcnt lgkmcnt(0) in front of the barrier.  The next stores into
+  //    Psi[CUR] are the lift stores of tile t + 1, from its step LAG on, behind that barrier: a fast wave cannot overtake a
+  //    slow wave's reads.  Behind the barrier tile t reads Psi[NXT] only, which every wave's lift has completed in front of it.
+  //  * The power table.  Tile t reads pow[NXT] at its lift reads, all in front of the barrier, and writes pow[CUR] at step
+  //    KP_RAW_STEP.  Tile t + 1 writes pow[NXT] - the table tile t read - only behind the barrier, and reads pow[CUR], which tile
+  //    t wrote in front of it.
+  //  * The final tile.  Behind its barrier the redirected reads fetch LDS that is initialised but stale (a Psi buffer of an
+  //    earlier tile, or the one-time zeros); nothing uses the values.  Keeping the reads is simpler than a branch.
+  constexpr int BS = TT.bs;
+  constexpr bool EBT = BS >= 0;
+  static_assert(!EBT || (EB && BS < NSTEP - 1 && BS >= (KT3 / 4 - 1) * NQ && BS >= KP_RAW_STEP && (NCH - 1) * SP + LAG <= BS && LAG <= SP),
+                "early barrier: behind the table store, the last lift store and the last k-step's first step, in front of the tile's last step");
+  constexpr int NAW = TUP ? NWT / 2 : NWT;           // weighted A operands per A group (TUP: tuples of two weights)
+  // operands in flight; EBT: they live across the tile boundary (the last steps of a tile request the next tile's first ones)
+  double bvs[NSTEP];
+  double bvs2[TUP ? NSTEP : 1];                      // TUP: the quad's second B operand (groups 2, 3)
+  double wt[NAW];
+  double avn0 = 0.0, avn1 = 0.0;                     // raw A fragments of the NEXT k-step (prefetched)
+  // B operands of quad step i of the tile in the Psi buffer at pb
+  auto load_b = [&](int pb, int i) __attribute__((always_inline)) {
+    bvs[i] = sm[pb + (i / NQ) * 4 * RS3 + bo[i % NQ]];
+    if constexpr (TUP) bvs2[i] = sm[pb + (i / NQ) * 4 * RS3 + bo2[i % NQ]];
+  };
+  // the NWT-1 weights of k-step kk, as 16-byte LDS reads (a pair each; immediate offsets, no address arithmetic);
+  // TUP: this lane's weight of each of the 5 tuples, 8-byte reads at immediate offsets from its own base
+  auto load_wt = [&](int pb, int kk) __attribute__((always_inline)) {
+    if constexpr (TUP) {
+#pragma unroll
+      for (int w = 0; w + 1 < NAW; w += 2) {
+        const double2 v = *reinterpret_cast<const double2*>(&sm[pb + kk * 4 * RS3 + wo + w]);
+        wt[w] = v.x;
+        wt[w + 1] = v.y;
+      }
+      wt[NAW - 1] = sm[pb + kk * 4 * RS3 + wo + NAW - 1];
+    } else {
+#pragma unroll
+      for (int w = 0; w < NWT - 1; w += 2) {
+        const double2 v = *reinterpret_cast<const double2*>(&sm[pb + kk * 4 * RS3 + wo + w]);
+        wt[w + 1] = v.x;
+        if (w + 2 < NWT) wt[w + 2] = v.y;
+      }
+    }
+  };
+  // a tile's first operands: the first PF steps' B operands, the A fragments and the weights of k-step 0
+  auto head_reads = [&](int pb, bool two_groups) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < PF; ++i) load_b(pb, i);
+    avn0 = sm[pb + ao0];
+    if (two_groups) avn1 = sm[pb + ao1];
+    load_wt(pb, 0);
+  };
 
   // one snapshot tile: MFMAs on Psi buffer CUR, lift of the next tile into buffer 1-CUR, raw prefetch two ahead.
   // QS = number of leading quads that use A group a0 (wave-uniform, selected once outside the loop).
@@ -607,6 +707,7 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
     constexpr int QS = decltype(qs_c)::value;
     using NXT = std::integral_constant<int, 1 - CUR>;
     constexpr int PB = CUR * PSIBUF3;
+    constexpr int NPB = (1 - CUR) * PSIBUF3;
     // The raw loads of the tile after next are issued INSIDE the MFMA loop (behind step KP_RAW_STEP), not here: registers the
     // compiler has spilled are reloaded at the top of the tile, and a scratch reload behind a global load waits for that
     // load too (vmcnt counts in order) - with the load up here every wave sat out its HBM latency at the start of every tile.
@@ -626,47 +727,15 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
         asm volatile("" : "+v"(wsb[j]));
       }
     }
-    constexpr int NAW = TUP ? NWT / 2 : NWT;           // weighted A operands per A group (TUP: tuples of two weights)
-    double bvs[NSTEP];
-    double bvs2[TUP ? NSTEP : 1];                      // TUP: the quad's second B operand (groups 2, 3)
     double aw[NAW];
-    double wt[NAW];
     double av1 = 0.0;
-    double avn0, avn1 = 0.0;                           // raw A fragments of the NEXT k-step (prefetched)
     auto weigh = [&](double av) __attribute__((always_inline)) {
 #pragma unroll
       for (int w = 0; w < NAW; ++w) {
         aw[w] = (!TUP && w == 0) ? av : av * wt[w];
       }
     };
-#pragma unroll
-    for (int i = 0; i < PF; ++i) {
-      bvs[i] = sm[PB + (i / NQ) * 4 * RS3 + bo[i % NQ]];
-      if constexpr (TUP) bvs2[i] = sm[PB + (i / NQ) * 4 * RS3 + bo2[i % NQ]];
-    }
-    avn0 = sm[PB + ao0];
-    if (QS < NQ) avn1 = sm[PB + ao1];
-    // the NWT-1 weights of k-step kk, as 16-byte LDS reads (a pair each; immediate offsets, no address arithmetic);
-    // TUP: this lane's weight of each of the 5 tuples, 8-byte reads at immediate offsets from its own base
-    auto load_wt = [&](int kk) __attribute__((always_inline)) {
-      if constexpr (TUP) {
-#pragma unroll
-        for (int w = 0; w + 1 < NAW; w += 2) {
-          const double2 v = *reinterpret_cast<const double2*>(&sm[PB + kk * 4 * RS3 + wo + w]);
-          wt[w] = v.x;
-          wt[w + 1] = v.y;
-        }
-        wt[NAW - 1] = sm[PB + kk * 4 * RS3 + wo + NAW - 1];
-      } else {
-#pragma unroll
-        for (int w = 0; w < NWT - 1; w += 2) {
-          const double2 v = *reinterpret_cast<const double2*>(&sm[PB + kk * 4 * RS3 + wo + w]);
-          wt[w + 1] = v.x;
-          if (w + 2 < NWT) wt[w + 2] = v.y;
-        }
-      }
-    };
-    load_wt(0);
+    if constexpr (!EBT) head_reads(PB, QS < NQ);       // (EBT: requested by the tile before, or in front of the first one)
 #pragma unroll
     for (int step = 0; step < NSTEP; ++step) {
       const int kk = step / NQ, q = step % NQ;
@@ -686,12 +755,21 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
         }
       }
       if (QS < NQ && q == QS) weigh(av1);
-      // fetch the weights one step before they are multiplied in (LDS reads are free, registers are not)
-      if (QS < NQ && QS > 1 && q == QS - 1) load_wt(kk);
-      if (q == NQ - 1 && kk + 1 < KT3 / 4) load_wt(kk + 1);
-      if (step + PF < NSTEP) {
-        bvs[step + PF] = sm[PB + ((step + PF) / NQ) * 4 * RS3 + bo[(step + PF) % NQ]];
-        if constexpr (TUP) bvs2[step + PF] = sm[PB + ((step + PF) / NQ) * 4 * RS3 + bo2[(step + PF) % NQ]];
+      // fetch the weights one step before they are multiplied in (LDS reads are free, registers are not); EBT: no later
+      // than the barrier step
+      const int wstep = kk * NQ + QS - 1;
+      if (QS < NQ && QS > 1 && step == (EBT && wstep > BS ? BS : wstep)) load_wt(PB, kk);
+      if (q == NQ - 1) {
+        if (kk + 1 < KT3 / 4) load_wt(PB, kk + 1);
+        else if constexpr (EBT) {                      // the next tile's weights and A fragments of k-step 0
+          load_wt(NPB, 0);
+          avn0 = sm[NPB + ao0];
+          if (QS < NQ) avn1 = sm[NPB + ao1];
+        }
+      }
+      if (step + PF < NSTEP) load_b(PB, step + PF);
+      else if constexpr (EBT) {
+        if (step > BS) load_b(NPB, step + PF - NSTEP);  // the next tile's first B operands, into slots this tile has used up
       }
       const double bv = bvs[step];
       const double bv2 = TUP ? bvs2[step] : 0.0;
@@ -711,6 +789,15 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
         if (step >= LAG && (step - LAG) % SP == 0 && (step - LAG) / SP < NCH) lift_write((step - LAG) / SP, NXT{});
         if (step % SP == 0 && step / SP < NCH) lift_read(step / SP, NXT{});
       }
+      if constexpr (EBT) {
+        if (step == BS) {
+          // the tile's barrier: behind this step's MFMAs and the last lift store (the table stores are inline assembly the
+          // compiler does not count: the explicit wait stays), then the B operands that were due in front of it
+          lds_store_barrier();
+#pragma unroll
+          for (int s = NSTEP - PF; s <= BS; ++s) load_b(NPB, s + PF - NSTEP);
+        }
+      }
       __builtin_amdgcn_sched_barrier(0);   // keep the hand-made software pipeline: no hoisting of later steps' LDS reads
     }
     if constexpr (!PRE) {
@@ -723,13 +810,16 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
     if constexpr (PRE) {
       store_pre(NXT{}, prereg);
       __syncthreads();
-    } else {
+    } else if constexpr (!EBT) {
       if constexpr (!INL) store_raw(cur_c, rawreg);
       lds_store_barrier();
     }
     if (PCS) project(NXT{});
   };
+  // nkt tiles, two per round (the buffer index is an immediate) and a remainder.  EBT: only the first tile's operands are
+  // requested here - the setup's last barrier has published Psi buffer 0 -, every tile requests those of the one behind it
   auto run_tiles = [&](auto qs_c) __attribute__((always_inline)) {
+    if constexpr (EBT) head_reads(0, decltype(qs_c)::value < NQ);
     int t = 0;
     for (; t + 1 < nkt; t += 2) {
       tile(B0{}, qs_c);
@@ -903,16 +993,25 @@ static bool gram3_tup(int bm) {
   return bm >= 2 && !off;              // (an even number of weights: m = 2 -> 6, m = 3 -> 10)
 }
 
-template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool TUP = false, bool P3 = false, bool LO = false>
-static hipError_t launch3c(const Gram3Args& a, int grid, size_t lds, hipStream_t st) {
+template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool TUP = false, bool P3 = false, bool LO = false, bool EB = false>
+static hipError_t launch3d(const Gram3Args& a, int grid, size_t lds, hipStream_t st) {
   static KpLdsCache lds_cache;
   {
     const size_t lds_max = (size_t)(LDS3_DOUBLES + (PCS ? LDS3_PCS_DOUBLES : 0) + (EXT ? LDS3_GAUSS_DOUBLES : 0)) * sizeof(double);
-    hipError_t e = kp_ensure_lds(lds_cache, (const void*)kp_gram3_kernel<NQ, BM, PCS, EXT, PRE, TUP, P3, LO>, lds_max);
+    hipError_t e = kp_ensure_lds(lds_cache, (const void*)kp_gram3_kernel<NQ, BM, PCS, EXT, PRE, TUP, P3, LO, EB>, lds_max);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((kp_gram3_kernel<NQ, BM, PCS, EXT, PRE, TUP, P3, LO>), dim3(grid), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((kp_gram3_kernel<NQ, BM, PCS, EXT, PRE, TUP, P3, LO, EB>), dim3(grid), dim3(256), lds, st, a);
   return hipGetLastError();
+}
+
+template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool TUP = false, bool P3 = false, bool LO = false>
+static hipError_t launch3c(const Gram3Args& a, int grid, size_t lds, hipStream_t st) {
+  // the early tile barrier, in every weight form of the in-kernel-lift monomial kernel whose tile has the room (gram3_launch_n sets eb only there)
+  if constexpr (!PCS && !EXT && !PRE && gram3_tile_timing(NQ, LO, true).bs >= 0) {
+    if (a.eb) return launch3d<NQ, BM, PCS, EXT, PRE, TUP, P3, LO, true>(a, grid, lds, st);
+  }
+  return launch3d<NQ, BM, PCS, EXT, PRE, TUP, P3, LO, false>(a, grid, lds, st);
 }
 
 template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false>
@@ -1087,6 +1186,12 @@ static bool gram3_lift_order_on() {
   return on;
 }
 
+// KP_GRAM3_EARLY_BARRIER=0 (read once): every tile keeps its barrier behind the last quad step (A/B runs, tests)
+static bool gram3_early_barrier_on() {
+  static const bool on = [] { const char* e = getenv("KP_GRAM3_EARLY_BARRIER"); return !e || atoi(e) != 0; }();
+  return on;
+}
+
 // The dictionary's lift slot table (kp_gram3_lift.h), built and uploaded on first use and kept with its circulant plan;
 // *out = nullptr: the dictionary keeps today's order (more jobs of three real factors than lift step 0 has slots).
 static int gram3_lift_table(kp_ctx* ctx, kp_basis* basis, const uint32_t** out) {
@@ -1258,6 +1363,12 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
     int rc = gram3_lift_table(ctx, basis, &a.lift);
     if (rc) return rc;
   }
+  // ... and, with the ordered lift, the tile's barrier in front of its last quad steps (EB) where the tile has the room.  Not for
+  // a plan with jobs of two A groups at NQ = 6, m = 3: those waves carry a second A fragment across the tile boundary, and two
+  // of their five tile loops then reload registers from scratch (the register table; one-A-group plans, fewer
+  // quads and fewer weights have none)
+  a.eb = !pre && b.k_pcs == 0 && !ext && plan.wpw == 4 && gram3_early_barrier_on() && gram3_tile_timing(plan.nq, a.lift != nullptr, true).bs >= 0 &&
+         (plan.two_group_jobs == 0 || plan.nq < 6 || BM < 3);
   const int grid = plan.nsuper * nsplit * n;
   // every event record is a barrier packet the command processor works through between two Gram kernels: the
   // pipelined path (ring_timing) keeps two (kernel start / end)
@@ -1317,6 +1428,8 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   ctx->timers[16] = (pre || ext || plan.wpw == 8) ? 0.0 : a.pow3 ? 3.0 : 4.0;
   // the lift order this launch ran: 1 the dictionary's slot table, 0 the order e = tid + 256 j (a form without the in-kernel monomial lift too)
   ctx->timers[20] = a.lift ? 1.0 : 0.0;
+  // where this launch's tiles had their barrier: 1 in front of the last quad steps, 0 behind the last one
+  ctx->timers[26] = a.eb ? 1.0 : 0.0;
   ctx->timers[15] = (double)plan.two_group_jobs;   // jobs of this launch's plan that span two A groups (0: a one-A-group plan)
   return KP_OK;
 }

@@ -39,6 +39,8 @@ struct Gram3Args {
   // the same form: its lift slot table (kp_gram3_lift.h: GRAM3_LIFT_SLOTS words) where the launch runs the ordered lift (LO),
   // nullptr where it runs the order e = tid + 256 j
   const uint32_t* lift = nullptr;
+  // the same form: the tile's barrier sits in front of its last quad steps (EB; kp_gram3.hip: gram3_tile_timing)
+  bool eb = false;
 };
 
 // one job per wave: kp_gram6_kernel<NQ, G4C> (kp_gram6.hip); hipErrorInvalidValue when no instantiation serves (nq, G4)
