@@ -109,7 +109,16 @@ int kp_device_info(const kp_ctx* ctx, char* name, int name_len, int* num_cu, int
  * Kronecker Gram launch had their workgroup barrier: 1 in front of the tile's last quad steps, whose MFMAs then run over the
  * latency of the next tile's first operand reads (the in-kernel-lift monomial form where timer 20 reads 1, with 4 to 6 quads per
  * wave; with 6 quads and three inputs only a plan without jobs of two A groups, timer 15 = 0), 0 behind the last step.  The results do not depend on it, bit for bit; environment variable
- * KP_GRAM3_EARLY_BARRIER=0 (read once) keeps placement 0 everywhere for A/B runs and tests. */
+ * KP_GRAM3_EARLY_BARRIER=0 (read once) keeps placement 0 everywhere for A/B runs and tests.  27: not a time - a bit mask of the
+ * kernels that the iteration loop of the most recent lasso batch launched (0 at its start, as timer 11; 0 when the homotopy took
+ * every value before the first iteration).  The projection, kp_lasso_project_kernel<EPT> with up to EPT elements of its slice of
+ * V per thread in registers: 0x1 EPT = 4, 0x2 EPT = 8, 0x4 EPT = 16, 0x8 EPT = 24, 0x10 EPT = 0 (the slice goes through memory);
+ * EPT covers ceil(ceil(n / wpv) / 1024) with n = W x columns and wpv = min(32, CUs / running values) workgroups per value.
+ * 0x20: the multi-launch form of the projection (kp_lasso_v_kernel, kp_lasso_newton_kernel, kp_lasso_final_kernel), run while
+ * more values are running than the device has CUs, after a reported exchange time-out and under KP_LASSO_NO_FUSED.  The
+ * product G [K_1 ... K_nv]: 0x40 kp_symm_gemm_kernel, 0x80 kp_symm_gemm2_kernel<RA, RB>, 0x100 kp_symm_gemm_naive_kernel; for
+ * the tiled kernel also 0x200 << (RA - 4), RA = 4 ... 8, and 0x4000, 0x8000, 0x10000, 0x20000 for RB = 2, 3, 4, 6.  A batch
+ * whose values retire sets the bits of every shape it passed through (the names: koopman_hip_lasso.h, KP_LASSO_RAN_*). */
 int kp_timer_get(const kp_ctx* ctx, int which, double* ms);
 /* Device pointer + byte size of the library stream's raw handle, for profilers/benchmarks
  * that want to bracket work with their own HIP events: returns hipStream_t as void*. */

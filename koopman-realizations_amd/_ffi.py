@@ -216,6 +216,19 @@ EIG_MAXN = 512                     # KP_EIG_MAXN
 EIG_WAVE_MAX = 32                  # KP_EIG_WAVE_MAX
 EIG_LDS_MAXN_VEC, EIG_LDS_MAXN_VAL = 99, 140      # KP_EIG_LDS_MAXN_VEC, KP_EIG_LDS_MAXN_VAL
 
+# what the lasso fit ran, and its product kernels alone (include/koopman_hip_lasso.h)
+LASSO_SIGNATURES = {
+    "kp_symm_product": (C.c_int, [vp, c_dp, c_dp, C.c_int, C.c_int, C.c_int, c_dp, c_ip]),
+}
+TIMER_LASSO_KERNELS = 27           # kp_timer_get slot: bit mask of the kernels the most recent lasso batch's iteration loop launched
+LASSO_RAN_EPT = {4: 0x1, 8: 0x2, 16: 0x4, 24: 0x8, 0: 0x10}      # KP_LASSO_RAN_EPT4 ... _EPT0: kp_lasso_project_kernel<EPT>
+LASSO_RAN_MULTI = 0x20             # KP_LASSO_RAN_MULTI: the multi-launch projection
+LASSO_RAN_SMALL, LASSO_RAN_TILED, LASSO_RAN_NAIVE = 0x40, 0x80, 0x100      # the product kernels
+LASSO_RAN_RA = {4: 0x200, 5: 0x400, 6: 0x800, 7: 0x1000, 8: 0x2000}       # KP_LASSO_RAN_RA4 << (RA - 4)
+LASSO_RAN_RB = {2: 0x4000, 3: 0x8000, 4: 0x10000, 6: 0x20000}             # KP_LASSO_RAN_RB2 ... _RB6
+SYMM_BY_SHAPE, SYMM_SMALL, SYMM_TILED_RB = 0, 1, 10                       # `variant` of kp_symm_product
+SYMM_RAN_SMALL, SYMM_RAN_NAIVE, SYMM_RAN_TILED = 1, 2, 1000               # its `ran`: tiled = 1000 + 10 RA + RB
+
 _lib = None
 
 
@@ -228,7 +241,7 @@ def lib():
                           "(make -C koopman-realizations_amd/csrc)")
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in (SIGNATURES | NMPC_SIGNATURES | OBSERVER_SIGNATURES | CT_SIGNATURES | ARM_SIGNATURES
-                                   | RSYS_SIGNATURES | VALIDATE_SIGNATURES | HORIZON_SIGNATURES | SIM_SIGNATURES | SPECTRUM_SIGNATURES).items():
+                                   | RSYS_SIGNATURES | VALIDATE_SIGNATURES | HORIZON_SIGNATURES | SIM_SIGNATURES | SPECTRUM_SIGNATURES | LASSO_SIGNATURES).items():
             fn = getattr(l, name)
             fn.restype, fn.argtypes = res, args
         _lib = l

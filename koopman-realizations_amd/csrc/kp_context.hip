@@ -162,7 +162,7 @@ int kp_dev_alloc_copy(kp_ctx* ctx, double** dst, const double* src, size_t n) {
 }
 
 extern "C" int kp_timer_get(const kp_ctx* c, int which, double* ms) {
-  if (!c || !ms || which < 0 || which >= 27) return KP_ERR_ARG;
+  if (!c || !ms || which < 0 || which >= 28) return KP_ERR_ARG;
   *ms = c->timers[which];
   return KP_OK;
 }

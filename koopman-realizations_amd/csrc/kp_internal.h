@@ -91,7 +91,7 @@ struct kp_ctx {
   int64_t hbm_bytes = 0;
   std::string name;
   mutable std::string err;
-  double timers[27] = {0};            // (26: where the tiles of the last Kronecker Gram launch had their barrier, 1 in front of the last quad steps, 0 behind the last one; kp_gram3.hip; 25: 1000 x model staged + the tile width of the most recent kp_validate_horizon, not a time; 24: its two kernels, ms; kp_validate_horizon.hip; 23: the regime of the most recent kp_eig, not a time; 22: its kernel, ms; kp_eig_general.hip; 21: kernel of the most recent kp_nmpc_simulate, ms; kp_nmpc.hip; 20: the lift order of the last Kronecker Gram launch, 1 the slot table, 0 tid + 256 j; kp_gram3.hip; 19: kernel of the most recent kp_mpc_simulate, ms; kp_mpc.hip; 18: entry, workgroup order and copies of the most recent batched solve, not a time; kp_solve.hip; 17: which panel kernel and substitution form the most recent rank-revealing solve ran, not a time; kp_pivchol.hip; 16: power-table entries per raw value written by the in-loop build of the last Kronecker Gram launch, 3 or 4; 15: jobs of the last Kronecker Gram launch's plan that span two A groups; kp_gram3.hip; 12: the group size of the Gram queue, 13: fits served by the launches of timer 7; kp_fit.hip; 14: kernel code of the most recent sweep call, not a time; kp_batch.hip)
+  double timers[28] = {0};            // (27: bit mask of the kernels the iteration loop of the most recent lasso batch launched, not a time; kp_lasso.hip; 26: where the tiles of the last Kronecker Gram launch had their barrier, 1 in front of the last quad steps, 0 behind the last one; kp_gram3.hip; 25: 1000 x model staged + the tile width of the most recent kp_validate_horizon, not a time; 24: its two kernels, ms; kp_validate_horizon.hip; 23: the regime of the most recent kp_eig, not a time; 22: its kernel, ms; kp_eig_general.hip; 21: kernel of the most recent kp_nmpc_simulate, ms; kp_nmpc.hip; 20: the lift order of the last Kronecker Gram launch, 1 the slot table, 0 tid + 256 j; kp_gram3.hip; 19: kernel of the most recent kp_mpc_simulate, ms; kp_mpc.hip; 18: entry, workgroup order and copies of the most recent batched solve, not a time; kp_solve.hip; 17: which panel kernel and substitution form the most recent rank-revealing solve ran, not a time; kp_pivchol.hip; 16: power-table entries per raw value written by the in-loop build of the last Kronecker Gram launch, 3 or 4; 15: jobs of the last Kronecker Gram launch's plan that span two A groups; kp_gram3.hip; 12: the group size of the Gram queue, 13: fits served by the launches of timer 7; kp_fit.hip; 14: kernel code of the most recent sweep call, not a time; kp_batch.hip)
   double gram_flops_per_pair = 0;
   // growable device workspaces
   void* ws[21] = {nullptr};     // slot 8: staging of the collectives, 9: rank-revealing solve, 10 / 11: Grams of the shadow dictionary of a dim_red fit, their half-transformed form

@@ -21,13 +21,25 @@
 #include <vector>
 
 #include "kp_internal.h"
+#include "koopman_hip_lasso.h"
 #include "kp_symm_gemm.h"
 
 // C (W x nc) = G (W x W, symmetric) * X (W x nc): kp_symm_gemm.h (k-blocked, double-buffered 4x4x4-MFMA tiles; a
 // stage-everything kernel for the few columns of the last running values)
-static hipError_t symm_gemm(hipStream_t st, const double* G, const double* X, int W, int nc, double* C) {
+static hipError_t symm_gemm(hipStream_t st, const double* G, const double* X, int W, int nc, double* C, int* ran = nullptr) {
   static const int variant = [] { const char* e = getenv("KP_SYMM_GEMM"); return e ? atoi(e) : 0; }();
-  return kp_symm_gemm2(st, G, X, W, nc, C, variant);
+  return kp_symm_gemm2(st, G, X, W, nc, C, variant, ran);
+}
+
+static_assert(SG2_RAN_SMALL == KP_SYMM_RAN_SMALL && SG2_RAN_NAIVE == KP_SYMM_RAN_NAIVE && SG2_RAN_TILED == KP_SYMM_RAN_TILED,
+              "kp_symm_gemm.h and koopman_hip_lasso.h name what a product call ran differently");
+// kp_timer_get(27) (include/koopman_hip.h): the bits of what a kp_symm_gemm2 call reported
+static unsigned lasso_product_bits(int ran) {
+  if (ran == SG2_RAN_SMALL) return KP_LASSO_RAN_SMALL;
+  if (ran == SG2_RAN_NAIVE) return KP_LASSO_RAN_NAIVE;
+  if (ran < SG2_RAN_TILED) return 0u;
+  const int ra = (ran - SG2_RAN_TILED) / 10, rb = (ran - SG2_RAN_TILED) % 10;
+  return KP_LASSO_RAN_TILED | (KP_LASSO_RAN_RA4 << (ra - 4)) | (rb == 2 ? KP_LASSO_RAN_RB2 : rb == 3 ? KP_LASSO_RAN_RB3 : rb == 4 ? KP_LASSO_RAN_RB4 : rb == 6 ? KP_LASSO_RAN_RB6 : 0u);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -903,6 +915,8 @@ int kp_lasso_batch_dev(kp_ctx* ctx, const double* G_dev, const double* C_dev, in
   bool path_tried = false;
   std::string path_err;
   ctx->timers[11] = 0.0;
+  ctx->timers[27] = 0.0;
+  unsigned ran_mask = 0u;                          // kernels launched by the iteration loop (kp_timer_get(27))
   while (it < max_iter && nba > 0) {
     if (path_after >= 0 && it >= path_after && !path_tried && W <= 512) {
       path_tried = true;
@@ -938,14 +952,15 @@ int kp_lasso_batch_dev(kp_ctx* ctx, const double* G_dev, const double* C_dev, in
         static const bool no_regs = getenv("KP_LASSO_V_IN_MEMORY") != nullptr;
 #define KP_LP_LAUNCH(E) hipLaunchKernelGGL(kp_lasso_project_kernel<E>, dim3(wpv, nba), dim3(LP_NT), 0, s, Kb[kc], Kb[ko], GKb[gc], GKb[go], C_dev, n, V, \
                                            Kb[kn], st, xchg, seq)
-        if (no_regs || ept > 24) KP_LP_LAUNCH(0);
-        else if (ept <= 4) KP_LP_LAUNCH(4);
-        else if (ept <= 8) KP_LP_LAUNCH(8);
-        else if (ept <= 16) KP_LP_LAUNCH(16);
-        else KP_LP_LAUNCH(24);
+        if (no_regs || ept > 24) { KP_LP_LAUNCH(0); ran_mask |= KP_LASSO_RAN_EPT0; }
+        else if (ept <= 4) { KP_LP_LAUNCH(4); ran_mask |= KP_LASSO_RAN_EPT4; }
+        else if (ept <= 8) { KP_LP_LAUNCH(8); ran_mask |= KP_LASSO_RAN_EPT8; }
+        else if (ept <= 16) { KP_LP_LAUNCH(16); ran_mask |= KP_LASSO_RAN_EPT16; }
+        else { KP_LP_LAUNCH(24); ran_mask |= KP_LASSO_RAN_EPT24; }
 #undef KP_LP_LAUNCH
         seq += LP_MAXPASS + 4;
       } else {
+        ran_mask |= KP_LASSO_RAN_MULTI;
         hipLaunchKernelGGL(kp_lasso_v_kernel, grid, dim3(256), 0, s, Kb[kc], Kb[ko], GKb[gc], GKb[go], C_dev, n, V, st);
         for (int p = 0; p < P; ++p) hipLaunchKernelGGL(kp_lasso_newton_kernel, grid, dim3(256), 0, s, V, n, st);
         hipLaunchKernelGGL(kp_lasso_final_kernel, grid, dim3(256), 0, s, V, Kb[kc], Kb[ko], n, Kb[kn], st);
@@ -955,7 +970,10 @@ int kp_lasso_batch_dev(kp_ctx* ctx, const double* G_dev, const double* C_dev, in
       std::swap(go, gc);
       const bool time_it = it == 0 && ctx->evp[4] && ctx->evp[5];    // the batch's first and widest product, for the bench line
       if (time_it) KP_HIP(ctx, hipEventRecord(ctx->evp[4], s));
-      KP_HIP(ctx, symm_gemm(s, prep->Gw, Kb[kc], W, nba * ncols, GKb[gc]));
+      int ran = 0;
+      KP_HIP(ctx, symm_gemm(s, prep->Gw, Kb[kc], W, nba * ncols, GKb[gc], &ran));
+      ran_mask |= lasso_product_bits(ran);
+      ctx->timers[27] = (double)ran_mask;
       if (time_it) {
         KP_HIP(ctx, hipEventRecord(ctx->evp[5], s));
         gemm_timed_cols = nba * ncols;
@@ -1128,4 +1146,29 @@ int kp_lasso_dev(kp_ctx* ctx, const double* G_dev, const double* C_dev, int W, i
                  double* K_dev, int* iters, kp_lasso_prep* prep) {
   double* dst[1] = {K_dev};
   return kp_lasso_batch_dev(ctx, G_dev, C_dev, W, ncols, &t, 1, max_iter, tol, dst, iters, prep);
+}
+
+// The product kernels alone (include/koopman_hip_lasso.h): host operands in and out on the context's stream, `variant` handed to
+// kp_symm_gemm2 as it is.  The result buffer is all-ones bytes (a NaN in every element) before the launch.
+extern "C" int kp_symm_product(kp_ctx* ctx, const double* G, const double* X, int W, int nc, int variant, double* C, int* ran) {
+  const bool var_ok = variant == KP_SYMM_BY_SHAPE || variant == KP_SYMM_SMALL || variant == 2 || variant == 3 || (variant >= 12 && variant <= 16);
+  if (!ctx || !G || !X || !C || W < 1 || nc < 1 || !var_ok)
+    return ctx ? ctx->fail(KP_ERR_ARG, "kp_symm_product: bad argument") : KP_ERR_ARG;
+  KP_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t bG = (size_t)W * W * 8, bX = (size_t)W * nc * 8;
+  char* ws = (char*)ctx->workspace(7, bG + 2 * bX);
+  if (!ws) return ctx->fail(KP_ERR_HIP, "kp_symm_product: out of device memory");
+  double* dG = (double*)ws;
+  double* dX = (double*)(ws + bG);
+  double* dC = (double*)(ws + bG + bX);
+  hipStream_t s = ctx->stream;
+  KP_HIP(ctx, hipMemcpyAsync(dG, G, bG, hipMemcpyHostToDevice, s));
+  KP_HIP(ctx, hipMemcpyAsync(dX, X, bX, hipMemcpyHostToDevice, s));
+  KP_HIP(ctx, hipMemsetAsync(dC, 0xff, bX, s));
+  int r = 0;
+  KP_HIP(ctx, kp_symm_gemm2(s, dG, dX, W, nc, dC, variant, &r));
+  KP_HIP(ctx, hipMemcpyAsync(C, dC, bX, hipMemcpyDeviceToHost, s));
+  KP_HIP(ctx, hipStreamSynchronize(s));
+  if (ran) *ran = r;
+  return KP_OK;
 }

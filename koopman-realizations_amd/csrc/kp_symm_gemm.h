@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+#include <algorithm>
 
 // kernel choice by output size in (16 rows x 1 column) units, measured with tools/symm_gemm_probe at W = 336 / 136 / 60:
 // up to SG2_SMALL_UNITS the stage-everything kernel wins (latency); above, the tiled kernel with 32 / 48 / 64 / 96 columns
@@ -260,8 +261,14 @@ static hipError_t sg2_launch(hipStream_t st, const double* G, const double* X, i
   return hipGetLastError();
 }
 
+// what a kp_symm_gemm2 call ran (its optional out-parameter; include/koopman_hip_lasso.h: KP_SYMM_RAN_*)
+#define SG2_RAN_SMALL 1
+#define SG2_RAN_NAIVE 2
+#define SG2_RAN_TILED 1000    // + 10 RA + RB
+
 template <int RB>
-static hipError_t sg2_launch_rb(hipStream_t st, const double* G, const double* X, int W, int nc, double* C) {
+static hipError_t sg2_launch_rb(hipStream_t st, const double* G, const double* X, int W, int nc, double* C, int* ran) {
+  if (ran) *ran = SG2_RAN_TILED + 10 * sg2_pick_ra(W) + RB;
   switch (sg2_pick_ra(W)) {
     case 4: return sg2_launch<4, RB>(st, G, X, W, nc, C);
     case 5: return sg2_launch<5, RB>(st, G, X, W, nc, C);
@@ -271,8 +278,10 @@ static hipError_t sg2_launch_rb(hipStream_t st, const double* G, const double* X
   }
 }
 
-static inline hipError_t kp_symm_gemm_small(hipStream_t st, const double* G, const double* X, int W, int nc, double* C) {
-  const size_t lds = (size_t)((W + 3) & ~3) * SG_RS * 8;
+static inline hipError_t kp_symm_gemm_small(hipStream_t st, const double* G, const double* X, int W, int nc, double* C, int* ran = nullptr) {
+  // the staged operands, and at least the 4 x 128 split-k partials that reuse the same LDS (W <= 8 stages fewer doubles than that)
+  const size_t lds = (size_t)std::max(((W + 3) & ~3) * SG_RS, 512) * 8;
+  if (ran) *ran = lds > 156 * 1024 ? SG2_RAN_NAIVE : SG2_RAN_SMALL;
   static bool attr_set[32] = {};
   int dev = 0;
   (void)hipGetDevice(&dev);
@@ -289,8 +298,10 @@ static inline hipError_t kp_symm_gemm_small(hipStream_t st, const double* G, con
   return hipGetLastError();
 }
 
-// variant: 0 = by shape; 1 = small-column kernel; 2 / 3 = tiled kernel with 32 / 64 columns per workgroup; 10 + RB = 16 RB columns
-static inline hipError_t kp_symm_gemm2(hipStream_t st, const double* G, const double* X, int W, int nc, double* C, int variant = 0) {
+// variant: 0 = by shape; 1 = small-column kernel; 2 / 3 = tiled kernel with 32 / 64 columns per workgroup; 10 + RB = 16 RB columns.
+// ran (may be NULL): what the call launched - SG2_RAN_SMALL, SG2_RAN_NAIVE or SG2_RAN_TILED + 10 RA + RB (0: nothing)
+static inline hipError_t kp_symm_gemm2(hipStream_t st, const double* G, const double* X, int W, int nc, double* C, int variant = 0, int* ran = nullptr) {
+  if (ran) *ran = 0;
   if (W <= 0 || nc <= 0) return hipSuccess;
   // the tiled kernel addresses X with 32-bit byte offsets from a uniform base (one VGPR per staged row)
   if ((uint64_t)nc * (uint64_t)W * 8u >= (1ull << 32)) variant = 1;
@@ -322,11 +333,11 @@ static inline hipError_t kp_symm_gemm2(hipStream_t st, const double* G, const do
     }
   }
   switch (variant) {
-    case 1: return kp_symm_gemm_small(st, G, X, W, nc, C);
-    case 2: case 12: return sg2_launch_rb<2>(st, G, X, W, nc, C);
-    case 13: return sg2_launch_rb<3>(st, G, X, W, nc, C);
-    case 15: return sg2_launch_rb<5>(st, G, X, W, nc, C);
-    case 16: return sg2_launch_rb<6>(st, G, X, W, nc, C);
-    default: return sg2_launch_rb<4>(st, G, X, W, nc, C);
+    case 1: return kp_symm_gemm_small(st, G, X, W, nc, C, ran);
+    case 2: case 12: return sg2_launch_rb<2>(st, G, X, W, nc, C, ran);
+    case 13: return sg2_launch_rb<3>(st, G, X, W, nc, C, ran);
+    case 15: return sg2_launch_rb<5>(st, G, X, W, nc, C, ran);
+    case 16: return sg2_launch_rb<6>(st, G, X, W, nc, C, ran);
+    default: return sg2_launch_rb<4>(st, G, X, W, nc, C, ran);
   }
 }

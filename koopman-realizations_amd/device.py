@@ -163,6 +163,18 @@ class Context:
                                            F.dptr(K), it.ctypes.data_as(F.c_ip)), self._h)
         return [np.asfortranarray(K[v].T) for v in range(len(tv))], it
 
+    def symm_product(self, G, X, variant=0):
+        """kp_symm_product: G X with the product kernels of the lasso iteration alone (G symmetric).  Returns (C, ran):
+        ran = F.SYMM_RAN_SMALL, F.SYMM_RAN_NAIVE or F.SYMM_RAN_TILED + 10 RA + RB; an element no lane stored is NaN."""
+        G = F.fcol(G); X = F.fcol(X)
+        W, nc = X.shape
+        if G.shape != (W, W):
+            raise ValueError("symm_product: G must be W x W for a W x nc X")
+        Cm = np.zeros((W, nc), order="F")
+        ran = C.c_int()
+        F.check(F.lib().kp_symm_product(self._h, F.dptr(G), F.dptr(X), W, nc, int(variant), F.dptr(Cm), C.byref(ran)), self._h)
+        return Cm, ran.value
+
     def fit_batch(self, basis, snaps, nb):
         """Least-squares fits of nb systems that share one dictionary (W <= 16): `snaps` holds the merged snapshot
         pairs, nb x Ns_each rows.  Returns K, G, C as (nb, W, W) arrays and the status vector."""

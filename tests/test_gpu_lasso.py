@@ -10,6 +10,7 @@ import pytest
 import koopman_realizations_amd as kra
 from oracle import koopman_oracle as ko
 from conftest import synth_pairs
+from _lasso_child import in_fresh_process
 from test_gpu_fit import make_basis
 
 pytestmark = pytest.mark.gpu
@@ -74,11 +75,20 @@ def test_lasso_matches_numpy_oracle_mid_size(ctx):
         assert ko.lasso_kkt_residual(G, C, K, f * l1) <= 1e-9 * np.abs(C).max()
 
 
-def test_lasso_without_polish_agrees(ctx, config3, monkeypatch):
-    """The active-set polish only ends the iteration early: the plain projected-gradient answer is the same optimum."""
+def test_lasso_without_polish_agrees(ctx, config3):
+    """The active-set polish only ends the iteration early: the plain projected-gradient answer (KP_LASSO_NO_POLISH is read
+    once per process, so it runs in a fresh interpreter) is the same optimum to 1e-9, after no fewer iterations.  Both runs
+    ask for tol = 1e-11: the iteration stops on its last STEP (change <= tol max|K|), and at a contraction of about 0.9 per
+    step the iterate is then some ten steps' worth from the optimum - at the default tol = 1e-10 the plain answer was measured
+    1.18e-9 max|K| from the polished one, which does not depend on tol."""
     G, C, l1 = config3["G"], config3["C"], config3["l1"]
-    Kp, itp = ctx.fit_lasso_batch(G, C, [0.3 * l1])
+    Kp, itp = ctx.fit_lasso_batch(G, C, [0.3 * l1], tol=1e-11)
     assert ko.lasso_kkt_residual(G, C, Kp[0], 0.3 * l1) <= 1e-10 * np.abs(C).max()     # polished: optimum to rounding
+    o = in_fresh_process([(G, C, [0.3 * l1])], {"KP_LASSO_NO_POLISH": "1"}, tol=1e-11)[0]
+    d = np.abs(o["K"][0, 0] - Kp[0]).max() / np.abs(Kp[0]).max()
+    print(f"lasso without polish: {int(o['it'][0, 0])} iterations against {int(itp[0])}, max |K - K polished| / max|K| = {d:.3e}")
+    assert d <= 1e-9
+    assert int(o["it"][0, 0]) >= int(itp[0])
 
 
 def test_lasso_grid_through_the_device_resident_gather(ctx, config3):
@@ -154,24 +164,8 @@ def test_one_shot_polish_without_active_set_rounds_gives_the_same_optimum(ctx, c
     """KP_LASSO_ROUNDS / KP_LASSO_COLD_START are read once per process, so the round-free path and the start from K = 0
     (default: from the least-squares solution) are exercised in a fresh interpreter: same optimum to 1e-9, no fewer
     iterations."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     G, C, l1 = config3["G"], config3["C"], config3["l1"]
     Kr, itr = ctx.fit_lasso_batch(G, C, [0.2 * l1])
-    script = ("import sys, numpy as np; sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + '/tests')\n"
-              "import koopman_realizations_amd as kra\n"
-              "d = np.load(sys.argv[2]); c = kra.Context(0)\n"
-              "K, it = c.fit_lasso_batch(d['G'], d['C'], [float(d['t'])])\n"
-              "np.savez(sys.argv[3], K=K[0], it=it[0])\n")
-    import tempfile
-    with tempfile.TemporaryDirectory() as td:
-        np.savez(os.path.join(td, "in.npz"), G=G, C=C, t=0.2 * l1)
-        env = dict(os.environ, **knob)
-        r = subprocess.run([sys.executable, "-c", script, root, os.path.join(td, "in.npz"), os.path.join(td, "out.npz")], env=env,
-                           capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        o = np.load(os.path.join(td, "out.npz"))
-        assert np.abs(o["K"] - Kr[0]).max() <= 1e-9 * np.abs(Kr[0]).max()
-        assert int(o["it"]) >= int(itr[0])
+    o = in_fresh_process([(G, C, [0.2 * l1])], knob, timeout=300)[0]
+    assert np.abs(o["K"][0, 0] - Kr[0]).max() <= 1e-9 * np.abs(Kr[0]).max()
+    assert int(o["it"][0, 0]) >= int(itr[0])

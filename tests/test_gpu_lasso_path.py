@@ -18,6 +18,7 @@ import pytest
 
 import koopman_realizations_amd as kra
 from oracle import koopman_oracle as ko
+from _lasso_child import in_fresh_process
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -89,21 +90,10 @@ def test_homotopy_against_the_numpy_homotopy_on_the_arm_gram(ctx, golden):
         assert abs(f(K) - f(Ko)) <= 1e-12 * abs(f(Ko))
 
 
-_SCRIPT = ("import sys, numpy as np; sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + '/tests')\n"
-           "import koopman_realizations_amd as kra\n"
-           "d = np.load(sys.argv[2]); c = kra.Context(0)\n"
-           "K, it = c.fit_lasso_batch(d['G'], d['C'], d['t'])\n"
-           "np.savez(sys.argv[3], K=np.stack(K), it=it, ms=c.timer(11))\n")
-
-
 def _in_fresh_process(G, C, t, env):
-    with tempfile.TemporaryDirectory() as td:
-        np.savez(os.path.join(td, "in.npz"), G=G, C=C, t=np.asarray(t, dtype=float))
-        r = subprocess.run([sys.executable, "-c", _SCRIPT, ROOT, os.path.join(td, "in.npz"), os.path.join(td, "out.npz")], env=dict(os.environ, **env),
-                           capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        o = np.load(os.path.join(td, "out.npz"))
-        return o["K"], o["it"], float(o["ms"])
+    """One kp_fit_lasso_batch call in a fresh interpreter (tests/_lasso_child.py): K, iterations, kp_timer_get(11)."""
+    o = in_fresh_process([(G, C, t)], env)[0]
+    return o["K"][0], o["it"][0], float(o["ms"][0])
 
 
 @pytest.mark.parametrize("global_inverse", [False, True], ids=["inverse_in_lds", "inverse_in_memory"])
