@@ -78,7 +78,7 @@ int kp_device_info(const kp_ctx* ctx, char* name, int name_len, int* num_cu, int
  * time - how many power-table entries per raw value (x, x^2, ...) the in-loop table build of the most recent Kronecker Gram launch's
  * kernel writes: 3 for a monomial dictionary without fourth powers and without a projection (its launches neither compute nor store
  * the x^4 entry that nothing reads), 4 otherwise; 0 for the forms that build no table in the loop (prelifted dim_red tiles, fourier /
- * gaussian entries, the eight-wave experiment).  The results do not depend on it, bit for bit; environment variable KP_GRAM3_POW3=0
+ * gaussian entries).  The results do not depend on it, bit for bit; environment variable KP_GRAM3_POW3=0
  * (read once) keeps four entries everywhere for A/B runs and tests.  17: not a time - which kernels the most recent rank-revealing
  * solve ran (the fall-back of kp_fit_solve, kp_fit, kp_fit_refine and kp_model_project for a rank-deficient Gram matrix; 0 before the
  * first one), as the decimal code 100 P + 10 S + R.  P, the panel kernel of the pivoted factorisation: 1 kp_pivchol_panel32_kernel<512>
@@ -98,8 +98,8 @@ int kp_device_info(const kp_ctx* ctx, char* name, int name_len, int* num_cu, int
  * 19: the kernel of the most recent batch of closed loops (koopman_hip_sim.h), ms.  20: not a time - the order in which the lift of
  * the most recent Kronecker Gram launch dealt its (item, snapshot pair) jobs over the lift slots: 1 the dictionary's slot table
  * (csrc/kp_gram3_lift.h: every job of three real factors in lift step 0, so that steps 1 and 2 read two table entries and multiply
- * once), 0 the order slot = job (a dictionary with more than 256 such jobs, the forms without the in-kernel monomial lift, the
- * KP_GRAM3_NOTUP form).  The results do not depend on it, bit for bit; environment variable KP_GRAM3_LIFT_ORDER=0 (read once) keeps
+ * once), 0 the order slot = job (a dictionary with more than 256 such jobs, the forms without the in-kernel monomial lift).
+ * The results do not depend on it, bit for bit; environment variable KP_GRAM3_LIFT_ORDER=0 (read once) keeps
  * order 0 everywhere for A/B runs and tests.  21: the kernel of the most recent batch of nonlinear closed loops (kp_nmpc_simulate,
  * koopman_hip_nmpc.h), ms.  22: the kernel of the most recent batched eigensolver call (kp_eig, koopman_hip_spectrum.h), ms.  23: not
  * a time - the regime that call ran: 1 a wave per matrix, 2 a workgroup with the matrix in LDS, 3 a workgroup with the matrix in a

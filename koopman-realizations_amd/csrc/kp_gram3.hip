@@ -138,18 +138,19 @@ constexpr Gram3TileTiming gram3_tile_timing(int nq, bool lo, bool eb) {
 // operand read per quad.  The weights sit in the 12 weight entries of a Psi row in tuple order (wslot), w_0 = 1 stored.
 // P3 (the in-kernel-lift monomial form without a projection; dictionaries of powers <= 3): the in-loop table build writes x, x^2, x^3 and no
 // x^4 entry that nothing reads - a v_mul_f64 and a ds_write_b64 less per wave and tile.
-// LO (the same form, its default weight form; kp_gram3_lift.h): the lift's jobs sit in the slots of a table built on the host - every job of three
+// LO (the same form; kp_gram3_lift.h): the lift's jobs sit in the slots of a table built on the host - every job of three
 // real factors in lift step 0, real factors first - so that lift steps 1 and 2 read two table entries and multiply once: 4
 // v_mul_f64 and 2 ds_read_b128 less per wave and tile, the same bits (a dropped factor is exactly 1.0).
-// EB (the same form, every weight form and plan): the tile's barrier sits at the end of quad step NSTEP - 1 - PF, not
+// EB (the same form, every plan): the tile's barrier sits at the end of quad step NSTEP - 1 - PF, not
 // behind the last one, the lift's chunks finish in front of it, and the operand reads that found nothing left to request (the
 // last PF steps' B operands, the last k-step's A fragment and weights) request the NEXT tile's first operands from the other
 // Psi buffer: the tile's last PF steps of MFMAs run from registers over that latency, and the next tile opens with its
 // operands present instead of a drained pipeline behind a barrier.  The same instructions, the same accumulation order.
 // gram3_tile_timing says which tiles take it (the ordered lift LO with NQ = 4, 5, 6); the others keep today's tile.
-template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool TUP = false, bool P3 = false, bool LO = false, bool EB = false>
+template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool P3 = false, bool LO = false, bool EB = false>
 __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
   constexpr int NWT = (BM + 1) * (BM + 2) / 2;
+  constexpr bool TUP = BM >= 2;
   static_assert(!EB || (!PCS && !EXT && !PRE), "early tile barrier: the in-kernel-lift monomial form");
   static_assert(!P3 || (!PCS && !EXT && !PRE), "three-entry table: the in-kernel-lift monomial form");
   static_assert(!LO || (!PCS && !EXT && !PRE), "ordered lift slots: the in-kernel-lift monomial form");
@@ -846,8 +847,8 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
 
 // Sums the partials of one (job, quad, weight) block vector in split order and scatters the
 // 4 blocks (4x4 each) into G and C.  lane l: block = (l>>2)&3, row r = l>>4, col c = l&3.
-// tup (kp_gram3_kernel<.., TUP = true>): accumulator w' = 2 p + h of a quad holds, in block b, weight 2 p + (b >> 1) against
-// group 2 h + (b & 1) of the quad.
+// BM >= 2 (the kernel's paired-weight form, TUP): accumulator w' = 2 p + h of a quad holds, in block b, weight 2 p + (b >> 1)
+// against group 2 h + (b & 1) of the quad.
 // blockDim.x / 64 = 4, 8 or 16 waves share the split sum (the launcher picks by the split count: a dim_red fit at the arm data's
 // size has 167 splits of 184 KB - four waves walked 42 dependent-latency loads each, 14 us for a 23 us Gram kernel), each wave
 // with four loads in flight; every order is fixed: bitwise reproducible.
@@ -858,7 +859,7 @@ __global__ __launch_bounds__(256, 2) void kp_gram3_kernel(Gram3Args a) {
 // 4 row + column - with the same four stores per entry; an element that is nobody's source writes nothing.  T blocks as ever.
 __global__ __launch_bounds__(1024) void kp_gram3_reduce_kernel(const double* __restrict__ part, int nsplit, int njobs, int NQ, int NWT,
                                                               int BM, const uint32_t* __restrict__ desc, int G4, int N, int W,
-                                                              double* __restrict__ G, double* __restrict__ C, int tup,
+                                                              double* __restrict__ G, double* __restrict__ C,
                                                               const uint32_t* __restrict__ dst_off, const uint32_t* __restrict__ dst) {
   const int idx = blockIdx.x;                 // (job*NQ + q)*NWT + w
   int w = idx % NWT;
@@ -885,7 +886,7 @@ __global__ __launch_bounds__(1024) void kp_gram3_reduce_kernel(const double* __r
   const uint32_t* jd = desc + (size_t)job * (1 + NQ);
   const int ga = q < (int)((jd[0] >> 16) & 255u) ? (int)(jd[0] & 255u) : (int)((jd[0] >> 8) & 255u);
   int gsel = (l >> 2) & 3;
-  if (tup) {
+  if (BM >= 2) {
     const int b = gsel;
     gsel = 2 * (w & 1) + (b & 1);
     w = (w & ~1) + (b >> 1);
@@ -929,7 +930,6 @@ __global__ __launch_bounds__(1024) void kp_gram3_reduce_kernel(const double* __r
 
 struct kp_gram3_plan {
   int G4 = 0, nq = 0, njobs = 0, nsuper = 0;
-  int wpw = 4;               // waves (jobs) per workgroup: 4 (kp_gram3_kernel) or 8 (kp_gram6_kernel, one workgroup per CU)
   int two_group_jobs = 0;    // jobs that span two A groups: their waves weigh two A fragments per k-step (kp_timer_get(15))
   uint32_t* desc = nullptr;  // device
   // cover plan (kp_gram3_cover.h): the reduction's destination lists, device; nullptr in a circulant plan
@@ -964,18 +964,17 @@ static hipError_t plan3_upload(uint32_t** dev, const std::vector<uint32_t>& host
 // (g, g+1, ..., g+floor(G4/2) mod G4; antipodal pairs once) and all G4 groups of psi_y.
 // All quads (A group, 4 B groups) of all rows form one list; a job (one wave) is nq CONSECUTIVE quads,
 // so it spans at most two A groups when nq <= quads per row, and whole workgroups (4 jobs) fill evenly (gram3_pack_rows).
-static int make_plan3(kp_ctx* ctx, int N, int nwt, int nq_cap, kp_gram3_plan** out, int wpw = 4, int nq_force = 0) {
+static int make_plan3(kp_ctx* ctx, int N, int nwt, int nq_cap, kp_gram3_plan** out) {
   kp_gram3_plan* p = new kp_gram3_plan();
-  p->wpw = wpw;
   const int G4 = (N + 3) / 4;
   p->G4 = G4;
   size_t maxq = 0;
   const std::vector<std::vector<int>> rows = gram3_circulant_rows(G4, &maxq);
   Gram3JobsHost jobs;
-  gram3_pack_rows(rows, G4, nwt, nq_cap, maxq, wpw, nq_force, &jobs);     // (quads, quads per job, job list: kp_gram3_cover.h)
+  gram3_pack_rows(rows, G4, nwt, nq_cap, maxq, &jobs);     // (quads, quads per job, job list: kp_gram3_cover.h)
   p->nq = jobs.nq;
   p->njobs = jobs.njobs;
-  p->nsuper = jobs.njobs / wpw;
+  p->nsuper = jobs.njobs / GRAM3_WAVES;
   p->two_group_jobs = gram3_two_group_jobs(jobs);
   hipError_t e = plan3_upload(&p->desc, jobs.desc);
   if (e != hipSuccess) {
@@ -986,47 +985,37 @@ static int make_plan3(kp_ctx* ctx, int N, int nwt, int nq_cap, kp_gram3_plan** o
   return KP_OK;
 }
 
-// m = 3 and m = 2 run the paired-weight form (TUP) of the kernel; KP_GRAM3_NOTUP=1 (read once) keeps the one-weight-per-operand form for
-// A/B measurements - the two write different partial layouts, the reduction is told which
-static bool gram3_tup(int bm) {
-  static const bool off = getenv("KP_GRAM3_NOTUP") != nullptr;
-  return bm >= 2 && !off;              // (an even number of weights: m = 2 -> 6, m = 3 -> 10)
-}
-
-template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool TUP = false, bool P3 = false, bool LO = false, bool EB = false>
+template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool P3 = false, bool LO = false, bool EB = false>
 static hipError_t launch3d(const Gram3Args& a, int grid, size_t lds, hipStream_t st) {
   static KpLdsCache lds_cache;
   {
     const size_t lds_max = (size_t)(LDS3_DOUBLES + (PCS ? LDS3_PCS_DOUBLES : 0) + (EXT ? LDS3_GAUSS_DOUBLES : 0)) * sizeof(double);
-    hipError_t e = kp_ensure_lds(lds_cache, (const void*)kp_gram3_kernel<NQ, BM, PCS, EXT, PRE, TUP, P3, LO, EB>, lds_max);
+    hipError_t e = kp_ensure_lds(lds_cache, (const void*)kp_gram3_kernel<NQ, BM, PCS, EXT, PRE, P3, LO, EB>, lds_max);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((kp_gram3_kernel<NQ, BM, PCS, EXT, PRE, TUP, P3, LO, EB>), dim3(grid), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((kp_gram3_kernel<NQ, BM, PCS, EXT, PRE, P3, LO, EB>), dim3(grid), dim3(256), lds, st, a);
   return hipGetLastError();
 }
 
-template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool TUP = false, bool P3 = false, bool LO = false>
+template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool P3 = false, bool LO = false>
 static hipError_t launch3c(const Gram3Args& a, int grid, size_t lds, hipStream_t st) {
-  // the early tile barrier, in every weight form of the in-kernel-lift monomial kernel whose tile has the room (gram3_launch_n sets eb only there)
+  // the early tile barrier, in the in-kernel-lift monomial kernel whose tile has the room (gram3_launch_n sets eb only there)
   if constexpr (!PCS && !EXT && !PRE && gram3_tile_timing(NQ, LO, true).bs >= 0) {
-    if (a.eb) return launch3d<NQ, BM, PCS, EXT, PRE, TUP, P3, LO, true>(a, grid, lds, st);
+    if (a.eb) return launch3d<NQ, BM, PCS, EXT, PRE, P3, LO, true>(a, grid, lds, st);
   }
-  return launch3d<NQ, BM, PCS, EXT, PRE, TUP, P3, LO, false>(a, grid, lds, st);
+  return launch3d<NQ, BM, PCS, EXT, PRE, P3, LO, false>(a, grid, lds, st);
 }
 
 template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false>
 static hipError_t launch3b(const Gram3Args& a, int grid, size_t lds, hipStream_t st) {
   if constexpr (!PCS && !EXT && !PRE) {
-    // the lift's jobs in the slots of the dictionary's table, in the default weight form (gram3_launch_n sets lift only there)
-    if (a.lift) return a.pow3 ? launch3c<NQ, BM, false, false, false, (BM >= 2), true, true>(a, grid, lds, st)
-                              : launch3c<NQ, BM, false, false, false, (BM >= 2), false, true>(a, grid, lds, st);
-    // no fourth power in the dictionary: the three-entry table, in the default weight form (gram3_launch_n sets pow3 only there)
-    if (a.pow3) return launch3c<NQ, BM, false, false, false, (BM >= 2), true>(a, grid, lds, st);
+    // the lift's jobs in the slots of the dictionary's table (gram3_launch_n sets lift only in this form)
+    if (a.lift) return a.pow3 ? launch3c<NQ, BM, false, false, false, true, true>(a, grid, lds, st)
+                              : launch3c<NQ, BM, false, false, false, false, true>(a, grid, lds, st);
+    // no fourth power in the dictionary: the three-entry table (gram3_launch_n sets pow3 only in this form)
+    if (a.pow3) return launch3c<NQ, BM, false, false, false, true>(a, grid, lds, st);
   }
-  if constexpr (BM >= 2) {
-    if (gram3_tup(BM)) return launch3c<NQ, BM, PCS, EXT, PRE, true>(a, grid, lds, st);
-  }
-  return launch3c<NQ, BM, PCS, EXT, PRE, false>(a, grid, lds, st);
+  return launch3c<NQ, BM, PCS, EXT, PRE>(a, grid, lds, st);
 }
 
 template <int NQ>
@@ -1081,6 +1070,14 @@ static bool gram3_prelift(const kp_basis* basis) {
   return gram3_ext(basis) && b.nzeta <= 16 && b.nzeta * (basis->ext_Dp + 2 * basis->ext_df) + basis->ext_ng + 1 <= 64;
 }
 
+// The forms of kp_gram3_kernel that a launch (pre: it reads a prelift buffer) of a dictionary runs.
+// In-kernel lift (the kernel's INL): the tile loop builds the power table - no fourier / gaussian table entries, no prelift buffer.
+static bool gram3_inl(const kp_basis* basis, bool pre) { return !pre && !gram3_ext(basis); }
+// The in-kernel-lift monomial form (the kernel's GRP): ... and no projection.  P3, LO, EB, the fits that share a launch and the
+// cover plan exist in this form only.  gram3_prelift serves projections and fourier / gaussian tables, so no launch of such a
+// dictionary has a prelift buffer: pre = false asks about the dictionary.
+static bool gram3_inl_mono(const kp_basis* basis, bool pre = false) { return gram3_inl(basis, pre) && basis->dev.k_pcs == 0; }
+
 bool kp_gram3_applicable(const kp_basis* basis) {
   const BasisDev& b = basis->dev;
   if (getenv("KP_NO_GRAM3")) return false;
@@ -1097,12 +1094,6 @@ bool kp_gram3_applicable(const kp_basis* basis) {
          b.m >= 1 && b.m <= 3 && (2 * (b.nzeta + b.m) + 1) * KT3 <= 256 && 2 * (b.nzeta + b.m) * 4 + 4 <= NIDMAX3;   // (+ 1: the constant's table row has a thread)
 }
 
-// eight-wave workgroups (kp_gram6.hip), a round 4 experiment: KP_GRAM6=1, read once
-static bool gram6_on() {
-  static const bool on = getenv("KP_GRAM6") != nullptr;
-  return on;
-}
-
 // the dictionary's plan, built on first use
 static int gram3_plan(kp_ctx* ctx, kp_basis* basis) {
   if (basis->plan3) return KP_OK;
@@ -1111,10 +1102,7 @@ static int gram3_plan(kp_ctx* ctx, kp_basis* basis) {
   // fourier / gaussian tables: the transcendental code's constants and temporaries cost ~40 registers, so fewer quads
   // (accumulators) per wave or the kernel spills (measured: 4 quads per wave is the fastest cap, tools/gram_shapes_probe.py)
   static const int ext_cap = [] { const char* e = getenv("KP_GRAM3_EXT_NQ"); return e ? atoi(e) : 4; }();
-  // round 4 experiment (KP_GRAM6=1): eight-wave workgroups, the weighted A operands in LDS (kp_gram6.hip)
-  const bool g6 = gram6_on() && BM == 3 && b.k_pcs == 0 && !gram3_ext(basis) && kp_gram6_serves(7, (N + 3) / 4);
-  return g6 ? make_plan3(ctx, N, NWT, 7, &basis->plan3, 8, 7)
-            : make_plan3(ctx, N, NWT, b.k_pcs > 0 ? 4 : gram3_ext(basis) ? ext_cap : 6, &basis->plan3);     // (one plan serves both forms of a dim_red / fourier / gaussian fit)
+  return make_plan3(ctx, N, NWT, b.k_pcs > 0 ? 4 : gram3_ext(basis) ? ext_cap : 6, &basis->plan3);     // (one plan serves both forms of a dim_red / fourier / gaussian fit)
 }
 
 // KP_GRAM3_COVER (read once): 0 - no launch takes a cover plan; unset or 1 - the launches of kp_fit's deferred-solve branch do
@@ -1131,8 +1119,8 @@ static bool gram3_onea_on() {
   return on;
 }
 
-// The dictionary's cover plan (kp_gram3_cover.h), built on first use: for the in-kernel-lift monomial form with four-wave
-// workgroups only - every column a pure monomial, no projection, no fourier / gaussian table entries - and KEPT only when it has
+// The dictionary's cover plan (kp_gram3_cover.h), built on first use: for the in-kernel-lift monomial form (gram3_inl_mono)
+// only - every column a pure monomial, no projection, no fourier / gaussian table entries - and KEPT only when it has
 // fewer jobs (whole workgroups) than the circulant plan and passes its own coverage check on the host.  *out = nullptr: this
 // dictionary runs the circulant plan everywhere.
 // A kept cover plan is replaced by the dictionary's one-A-group plan (gram3_onea_build: same quads per job, no job spans two A
@@ -1146,9 +1134,9 @@ static int gram3_cover_plan(kp_ctx* ctx, kp_basis* basis, kp_gram3_plan** out) {
     circ.cover_tried = true;
     const BasisDev& b = basis->dev;
     const int N = b.N, NWT = (b.m + 1) * (b.m + 2) / 2;
-    if (circ.wpw != 4 || b.k_pcs != 0 || gram3_ext(basis) || !basis->fast || b.nfull != N || (int)basis->h_recipes.size() != N) return KP_OK;
+    if (!gram3_inl_mono(basis) || !basis->fast || b.nfull != N || (int)basis->h_recipes.size() != N) return KP_OK;
     Gram3CoverHost cov;
-    if (!gram3_cover_build(basis->h_recipes.data(), N, basis->pow_depth, NWT, 6, circ.wpw, &cov) || cov.jobs.njobs >= circ.njobs) return KP_OK;
+    if (!gram3_cover_build(basis->h_recipes.data(), N, basis->pow_depth, NWT, 6, &cov) || cov.jobs.njobs >= circ.njobs) return KP_OK;
     if (gram3_onea_on()) {
       Gram3CoverHost one;
       if (gram3_onea_build(basis->h_recipes.data(), N, basis->pow_depth, cov, &one) && one.jobs.nq == cov.jobs.nq && one.jobs.njobs <= cov.jobs.njobs) cov = std::move(one);
@@ -1158,7 +1146,7 @@ static int gram3_cover_plan(kp_ctx* ctx, kp_basis* basis, kp_gram3_plan** out) {
     p->two_group_jobs = gram3_two_group_jobs(cov.jobs);
     p->nq = cov.jobs.nq;
     p->njobs = cov.jobs.njobs;
-    p->nsuper = cov.jobs.njobs / circ.wpw;
+    p->nsuper = cov.jobs.njobs / GRAM3_WAVES;
     p->cover_tried = true;
     hipError_t e = plan3_upload(&p->desc, cov.jobs.desc);
     if (e == hipSuccess) e = plan3_upload(&p->dst_off, cov.dst_off);
@@ -1228,10 +1216,10 @@ static int gram3_plan_for(kp_ctx* ctx, kp_basis* basis, bool deferred, kp_gram3_
   return KP_OK;
 }
 
-// workgroup slots of the chip for this plan's kernel
-static int64_t gram3_slots(const kp_ctx* ctx, const kp_gram3_plan& plan, int* ncu_out = nullptr, int* wgpcu_out = nullptr) {
+// workgroup slots of the chip for kp_gram3_kernel
+static int64_t gram3_slots(const kp_ctx* ctx, int* ncu_out = nullptr, int* wgpcu_out = nullptr) {
   int ncu = ctx->num_cu > 0 ? ctx->num_cu : 256;
-  int wg_per_cu = plan.wpw == 8 ? 1 : 2;              // __launch_bounds__(256, 2): two workgroups share a CU (kp_gram6: one of eight waves)
+  int wg_per_cu = 2;                                  // __launch_bounds__(256, 2): two workgroups share a CU
   if (const char* ov = getenv("KP_GRAM3_WGPCU")) wg_per_cu = std::max(1, atoi(ov));
   if (ncu_out) *ncu_out = ncu;
   if (wgpcu_out) *wgpcu_out = wg_per_cu;
@@ -1239,7 +1227,7 @@ static int64_t gram3_slots(const kp_ctx* ctx, const kp_gram3_plan& plan, int* nc
 }
 
 // Fits that may share a Gram launch (kp_fit.hip's queue of pipelined fits): the in-kernel-lift monomial form of kp_gram3_kernel -
-// no projection, no fourier / gaussian table entries, hence no prelift buffer either - with four-wave workgroups; and only while
+// no projection, no fourier / gaussian table entries, hence no prelift buffer either (gram3_inl_mono); and only while
 // a lone launch's splits are shorter than KP_GRAM_GROUP_MAX_KPS tiles.  What sharing saves is a fixed cost per fit (head, write-out
 // and reduction of one accumulator set per wave slot: ~30 us at W = 336, some 15 tile times); what it costs is whole-split
 // granularity, 1 - 1.4 % of the kernel time (a fit of a group of 8 gets 9 of the 73 splits: 504 of 512 slots) - measured at
@@ -1249,11 +1237,11 @@ static int64_t gram3_slots(const kp_ctx* ctx, const kp_gram3_plan& plan, int* nc
 bool kp_gram3_groupable(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapshots* s) {
   kp_basis* basis = const_cast<kp_basis*>(basis_c);
   const BasisDev& b = basis->dev;
-  if (!(kp_gram3_applicable(basis) && b.k_pcs == 0 && !gram3_ext(basis) && !gram6_on() && s->nzeta == b.nzeta && s->m == b.m)) return false;
+  if (!(kp_gram3_applicable(basis) && gram3_inl_mono(basis) && s->nzeta == b.nzeta && s->m == b.m)) return false;
   kp_gram3_plan* plan = nullptr;                 // (the plan the queue's launch will run: kp_gram3_launch_group)
-  if (gram3_plan_for(ctx, basis, true, &plan) != KP_OK || plan->wpw == 8) return false;      // (a plan that cannot be built: the immediate dispatch reports it)
+  if (gram3_plan_for(ctx, basis, true, &plan) != KP_OK) return false;      // (a plan that cannot be built: the immediate dispatch reports it)
   static const int64_t max_kps = [] { const char* e = getenv("KP_GRAM_GROUP_MAX_KPS"); return e ? (int64_t)atoll(e) : (int64_t)512; }();
-  const int64_t ktiles = (s->Ns + KT3 - 1) / KT3, nsplit = std::max<int64_t>(1, gram3_slots(ctx, *plan) / plan->nsuper);
+  const int64_t ktiles = (s->Ns + KT3 - 1) / KT3, nsplit = std::max<int64_t>(1, gram3_slots(ctx) / plan->nsuper);
   return (ktiles + nsplit - 1) / nsplit < max_kps;
 }
 
@@ -1280,7 +1268,7 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   
   int64_t ktiles = (s->Ns + KT3 - 1) / KT3;
   int ncu, wg_per_cu;
-  const int64_t slots = gram3_slots(ctx, plan, &ncu, &wg_per_cu);
+  const int64_t slots = gram3_slots(ctx, &ncu, &wg_per_cu);
   // (per fit: the fits of a group launch share the chip)
   int nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(ktiles, slots / plan.nsuper / n > 0 ? slots / plan.nsuper / n : 1));
   int kps = (int)((ktiles + nsplit - 1) / nsplit);
@@ -1309,7 +1297,7 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   // (tools/arm_shape_latency.py with KP_GRAM3_PRELIFT_MIN_NS=0).  Below a few thousand pairs the second launch is not worth it.
   static const int64_t pre_min_ns = [] { const char* e = getenv("KP_GRAM3_PRELIFT_MIN_NS"); return e ? (int64_t)atoll(e) : (int64_t)6000; }();
   bool pre = gram3_prelift(basis) && s->Ns >= pre_min_ns;
-  if (n > 1 && (pre || b.k_pcs > 0 || ext || plan.wpw == 8)) return ctx->fail(KP_ERR_ARG, "kp_fit_gram: these fits cannot share a launch");
+  if (n > 1 && !gram3_inl_mono(basis, pre)) return ctx->fail(KP_ERR_ARG, "kp_fit_gram: these fits cannot share a launch");
   const int pre_rl = 8 * plan.G4 + 12;
   double* pre_buf = nullptr;
   if (pre) {
@@ -1356,10 +1344,11 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   a.pre_rl = pre_rl;
   a.nsplit_fit = nsplit;
   for (int f = 0; f < n; ++f) a.grp[f] = Gram3Src{ss[f]->alpha, ss[f]->beta, ss[f]->u};
-  // the in-kernel-lift monomial form without a projection, in its default weight form: three table entries where no recipe reads a fourth
-  a.pow3 = !pre && b.k_pcs == 0 && !ext && plan.wpw == 4 && basis->pow_depth <= 3 && (BM < 2 || gram3_tup(BM)) && gram3_pow3_on();
+  const bool mono = gram3_inl_mono(basis, pre);
+  // the in-kernel-lift monomial form: three table entries where no recipe reads a fourth
+  a.pow3 = mono && basis->pow_depth <= 3 && gram3_pow3_on();
   // ... and, in the same form, the lift's jobs in the slots of the dictionary's table (LO) where it has one
-  if (!pre && b.k_pcs == 0 && !ext && plan.wpw == 4 && (BM < 2 || gram3_tup(BM)) && gram3_lift_order_on()) {
+  if (mono && gram3_lift_order_on()) {
     int rc = gram3_lift_table(ctx, basis, &a.lift);
     if (rc) return rc;
   }
@@ -1367,7 +1356,7 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   // a plan with jobs of two A groups at NQ = 6, m = 3: those waves carry a second A fragment across the tile boundary, and two
   // of their five tile loops then reload registers from scratch (the register table; one-A-group plans, fewer
   // quads and fewer weights have none)
-  a.eb = !pre && b.k_pcs == 0 && !ext && plan.wpw == 4 && gram3_early_barrier_on() && gram3_tile_timing(plan.nq, a.lift != nullptr, true).bs >= 0 &&
+  a.eb = mono && gram3_early_barrier_on() && gram3_tile_timing(plan.nq, a.lift != nullptr, true).bs >= 0 &&
          (plan.two_group_jobs == 0 || plan.nq < 6 || BM < 3);
   const int grid = plan.nsuper * nsplit * n;
   // every event record is a barrier packet the command processor works through between two Gram kernels: the
@@ -1401,8 +1390,7 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   else if (pre)
     KP_HIP(ctx, kp_gram3_prelift_launch(BM, s->alpha, s->beta, s->u, s->Ns, ktiles * KT3, b.nzeta, basis->pow_depth, b.nfull, b.k_pcs, N, plan.G4,
                                         (const uint32_t*)basis->d_recipes, (const double*)basis->d_pcsT, pre_buf, pre_rl, ctx->stream));
-  if (plan.wpw == 8) e = kp_gram6_launch_kernel(a, plan.nq, grid, ctx->stream);
-  else switch (plan.nq) {
+  switch (plan.nq) {
     case 1: e = launch3<1>(a, BM, grid, lds, ctx->stream); break;
     case 2: e = launch3<2>(a, BM, grid, lds, ctx->stream); break;
     case 3: e = launch3<3>(a, BM, grid, lds, ctx->stream); break;
@@ -1413,7 +1401,7 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   KP_HIP(ctx, e);
   if (timed) KP_HIP(ctx, hipEventRecord(ev_end, ctx->stream));
   hipLaunchKernelGGL(kp_gram3_reduce_kernel, dim3(plan.njobs * plan.nq * NWT, n), dim3(nsplit >= 128 ? 1024 : nsplit >= 32 ? 512 : 256), 0, ctx->stream, part, nsplit, plan.njobs,
-                     plan.nq, NWT, BM, plan.desc, plan.G4, N, W, GC_dev, GC_dev + (size_t)W * W, plan.wpw != 8 && gram3_tup(BM) ? 1 : 0, plan.dst_off, plan.dst);
+                     plan.nq, NWT, BM, plan.desc, plan.G4, N, W, GC_dev, GC_dev + (size_t)W * W, plan.dst_off, plan.dst);
   KP_HIP(ctx, hipGetLastError());
   if (ev_red) KP_HIP(ctx, hipEventRecord(ev_red, ctx->stream));
   if (!ctx->ring_timing) {
@@ -1425,7 +1413,7 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   // each; dim_red: + the projection pcs' psi of every workgroup of a split (2 x nfull4 / 4 MFMAs per wave and tile)
   ctx->timers[10] = (double)plan.njobs * plan.nq * NWT * 128.0 + (b.k_pcs > 0 && !pre ? (double)plan.nsuper * nfull4 * 128.0 : 0.0);
   // table entries per raw value that the in-loop build of this launch's kernel writes (0: a form without that build)
-  ctx->timers[16] = (pre || ext || plan.wpw == 8) ? 0.0 : a.pow3 ? 3.0 : 4.0;
+  ctx->timers[16] = !gram3_inl(basis, pre) ? 0.0 : a.pow3 ? 3.0 : 4.0;
   // the lift order this launch ran: 1 the dictionary's slot table, 0 the order e = tid + 256 j (a form without the in-kernel monomial lift too)
   ctx->timers[20] = a.lift ? 1.0 : 0.0;
   // where this launch's tiles had their barrier: 1 in front of the last quad steps, 0 behind the last one

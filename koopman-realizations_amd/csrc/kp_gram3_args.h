@@ -1,5 +1,5 @@
-// Arguments of the Kronecker Gram kernels (kp_gram3.hip: 4-wave workgroups; kp_gram6.hip: 8-wave workgroups with the weighted
-// A operands in LDS), shared so that kp_gram3_launch can hand one plan / partial layout to either.
+// Arguments of the Kronecker Gram kernel (kp_gram3_kernel, kp_gram3.hip) and the launch prototypes of the prelift kernels
+// (kp_gram3_prelift.hip) that fill its row buffer.
 #pragma once
 #include "kp_internal.h"
 
@@ -42,10 +42,6 @@ struct Gram3Args {
   // the same form: the tile's barrier sits in front of its last quad steps (EB; kp_gram3.hip: gram3_tile_timing)
   bool eb = false;
 };
-
-// one job per wave: kp_gram6_kernel<NQ, G4C> (kp_gram6.hip); hipErrorInvalidValue when no instantiation serves (nq, G4)
-bool kp_gram6_serves(int nq, int G4);
-hipError_t kp_gram6_launch_kernel(const Gram3Args& a, int nq, int grid, hipStream_t st);
 
 // kp_gram3_prelift.hip: the projection matrix as [full column][32 components] (zero padded), and the econ lift of every snapshot in the
 // tile layout of Gram3Args::pre

@@ -35,10 +35,12 @@ inline std::vector<std::vector<int>> gram3_circulant_rows(int G4, size_t* maxq) 
   return rows;
 }
 
+constexpr int GRAM3_WAVES = 4;       // waves (jobs) of a workgroup of kp_gram3_kernel
+
 // rows[g]: the B groups (psi_x groups < G4, psi_y groups G4 + h) that A group g is multiplied with.  All quads (A group, 4 B
 // groups) of all rows form one list; a job (one wave) is nq CONSECUTIVE quads, so it spans at most two A groups when nq <= the
-// quads of every row (nq_rows: the bound the caller's rows give), and whole workgroups (wpw jobs) fill evenly.
-inline void gram3_pack_rows(const std::vector<std::vector<int>>& rows, int G4, int nwt, int nq_cap, size_t nq_rows, int wpw, int nq_force, Gram3JobsHost* out) {
+// quads of every row (nq_rows: the bound the caller's rows give), and whole workgroups (GRAM3_WAVES jobs) fill evenly.
+inline void gram3_pack_rows(const std::vector<std::vector<int>>& rows, int G4, int nwt, int nq_cap, size_t nq_rows, Gram3JobsHost* out) {
   const int ZG = 2 * G4;
   std::vector<std::pair<int, uint32_t>> quads;
   for (int g = 0; g < G4; ++g) {
@@ -63,8 +65,7 @@ inline void gram3_pack_rows(const std::vector<std::vector<int>>& rows, int G4, i
     double cost = (double)waves * (c * nwt * 33.0 + 400.0);
     if (cost < best) { best = cost; nq = c; }
   }
-  if (nq_force > 0) nq = nq_force;
-  else if (const char* ov = getenv("KP_GRAM3_NQ")) {   // tuning override
+  if (const char* ov = getenv("KP_GRAM3_NQ")) {   // tuning override
     int v = atoi(ov);
     if (v >= 1 && v <= std::min(NQMAX, nq_cap) && (size_t)v <= nq_rows) nq = v;
   }
@@ -73,7 +74,7 @@ inline void gram3_pack_rows(const std::vector<std::vector<int>>& rows, int G4, i
   out->desc.clear();
   int njobs = 0;
   const uint32_t zq = (uint32_t)ZG * 0x01010101u;
-  for (int q0 = 0; q0 < TQ || njobs % wpw; q0 += nq) {
+  for (int q0 = 0; q0 < TQ || njobs % GRAM3_WAVES; q0 += nq) {
     int a0 = q0 < TQ ? quads[q0].first : 0, a1 = a0, qs = nq;
     for (int q = 0; q < nq; ++q)
       if (q0 + q < TQ && quads[q0 + q].first != a0) { a1 = quads[q0 + q].first; qs = q; break; }
@@ -94,7 +95,7 @@ struct Gram3CoverHost {
 
 // The cover plan of a dictionary of N monomial columns (recipes: <= 4 power-table ids v D + e - 1 per column, 255 = none).
 // False when the plan cannot be built or fails its own coverage check: the caller stays on the circulant plan.
-inline bool gram3_cover_build(const uint32_t* recipes, int N, int D, int nwt, int nq_cap, int wpw, Gram3CoverHost* out) {
+inline bool gram3_cover_build(const uint32_t* recipes, int N, int D, int nwt, int nq_cap, Gram3CoverHost* out) {
   if (N < 1 || D < 1 || N > 4 * 127) return false;
   const int G4 = (N + 3) / 4;
   int nv = 1;
@@ -169,7 +170,7 @@ inline bool gram3_cover_build(const uint32_t* recipes, int N, int D, int nwt, in
     for (int h = 0; h < G4; ++h) rows[g].push_back(G4 + h);     // T groups follow the S groups of a row
     minq = std::min(minq, (rows[g].size() + 3) / 4);
   }
-  gram3_pack_rows(rows, G4, nwt, nq_cap, minq, wpw, 0, &out->jobs);
+  gram3_pack_rows(rows, G4, nwt, nq_cap, minq, &out->jobs);
   out->npairs = (int)chosen.size();
   out->nmonos = nm;
 

@@ -119,8 +119,7 @@ print("EARLY_BARRIER_CHILD_OK")
 
 def _child(out, early, nq):
     env = {k: v for k, v in os.environ.items() if k not in ("KP_GRAM3_COVER", "KP_GRAM3_ONEA", "KP_GRAM3_POW3", "KP_GRAM3_WGPCU", "KP_GRAM3_NQ",
-                                                             "KP_GRAM3_NOTUP", "KP_GRAM6", "KP_GRAM3_LIFT_ORDER", "KP_GRAM_GROUP",
-                                                             "KP_GRAM3_EARLY_BARRIER")}
+                                                             "KP_GRAM3_LIFT_ORDER", "KP_GRAM_GROUP", "KP_GRAM3_EARLY_BARRIER")}
     if early is not None:
         env["KP_GRAM3_EARLY_BARRIER"] = str(early)
     if nq is not None:

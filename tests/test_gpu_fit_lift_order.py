@@ -96,7 +96,7 @@ print("LIFT_ORDER_CHILD_OK")
 
 def _child(out, lift_order):
     env = {k: v for k, v in os.environ.items() if k not in ("KP_GRAM3_COVER", "KP_GRAM3_ONEA", "KP_GRAM3_POW3", "KP_GRAM3_WGPCU", "KP_GRAM3_NQ",
-                                                             "KP_GRAM3_NOTUP", "KP_GRAM6", "KP_GRAM3_LIFT_ORDER", "KP_GRAM_GROUP")}
+                                                             "KP_GRAM3_LIFT_ORDER", "KP_GRAM_GROUP")}
     if lift_order is not None:
         env["KP_GRAM3_LIFT_ORDER"] = str(lift_order)
     r = subprocess.run([sys.executable, "-c", _CHILD, ROOT, out], capture_output=True, text=True, timeout=300, env=env)

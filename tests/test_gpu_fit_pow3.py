@@ -101,8 +101,7 @@ print("POW3_CHILD_OK")
 
 
 def _child(out, pow3):
-    env = {k: v for k, v in os.environ.items() if k not in ("KP_GRAM3_COVER", "KP_GRAM3_ONEA", "KP_GRAM3_POW3", "KP_GRAM3_WGPCU", "KP_GRAM3_NQ",
-                                                             "KP_GRAM3_NOTUP", "KP_GRAM6")}
+    env = {k: v for k, v in os.environ.items() if k not in ("KP_GRAM3_COVER", "KP_GRAM3_ONEA", "KP_GRAM3_POW3", "KP_GRAM3_WGPCU", "KP_GRAM3_NQ")}
     env["KP_GRAM3_COVER"] = "2"
     if pow3 is not None:
         env["KP_GRAM3_POW3"] = str(pow3)

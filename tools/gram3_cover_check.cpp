@@ -59,9 +59,9 @@ int main(int argc, char** argv) {
   size_t maxq = 0;
   const std::vector<std::vector<int>> crow = gram3_circulant_rows(G4, &maxq);     // (make_plan3's)
   Gram3JobsHost circ;
-  gram3_pack_rows(crow, G4, nwt, 6, maxq, 4, 0, &circ);
+  gram3_pack_rows(crow, G4, nwt, 6, maxq, &circ);
   Gram3CoverHost cov;
-  const bool ok = gram3_cover_build(rec.data(), N, D, nwt, 6, 4, &cov);
+  const bool ok = gram3_cover_build(rec.data(), N, D, nwt, 6, &cov);
   printf("{\"N\": %d, \"G4\": %d, \"nwt\": %d, \"circ\": {\"quads\": %d, \"nq\": %d, \"njobs\": %d, \"nsuper\": %d}, "
          "\"cover_ok\": %s, \"cover\": {\"monomials\": %d, \"pairs\": %d, \"quads\": %d, \"nq\": %d, \"njobs\": %d, \"nsuper\": %d, \"dst\": %zu}, \"kept\": %s}\n",
          N, G4, nwt, circ.nquads, circ.nq, circ.njobs, circ.njobs / 4, ok ? "true" : "false", cov.nmonos, cov.npairs, cov.jobs.nquads, cov.jobs.nq,

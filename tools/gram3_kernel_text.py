@@ -2,10 +2,10 @@
 """Instruction counts of one kp_gram3_kernel instantiation from the compiler's text (the register table of DESIGN 6.7 / 6.8):
 
     hipcc -S --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -Iinclude -I<csrc> <csrc>/kp_gram3.hip -o kp_gram3.s
-    python3 tools/gram3_kernel_text.py kp_gram3.s 6 3 0 0 0 1 1 1 [1]
+    python3 tools/gram3_kernel_text.py kp_gram3.s 6 3 0 0 0 1 1 1
 
-The arguments behind the file are the template arguments NQ BM PCS EXT PRE TUP P3 LO [EB] (EB absent: a text from before the early
-barrier).  Prints one JSON line: v_mfma, v_mul_f64, ds_read*, ds_write*, scratch_*, s_barrier in the whole instantiation; VGPRs
+The arguments behind the file are the template arguments NQ BM PCS EXT PRE P3 LO EB (a text from before HISTORY.md's "Opt-in forms
+of the Kronecker Gram kernel" has TUP behind PRE; one from before the early barrier no EB).  Prints one JSON line: v_mfma, v_mul_f64, ds_read*, ds_write*, scratch_*, s_barrier in the whole instantiation; VGPRs
 and scratch bytes from the kernel descriptor's comments; and per tile loop (a backward branch whose body holds MFMAs) the
 number of tile bodies' worth of MFMAs, of vector instructions (MFMAs included) and of scratch accesses in it."""
 import json

@@ -66,7 +66,7 @@ int main(int argc, char** argv) {
   }
   Gram3CoverHost cov;
   double t0 = now_ms();
-  const bool cover_ok = gram3_cover_build(rec.data(), N, D, nwt, 6, 4, &cov);
+  const bool cover_ok = gram3_cover_build(rec.data(), N, D, nwt, 6, &cov);
   const double cover_ms = now_ms() - t0;
   Gram3CoverHost one;
   std::vector<int> hubs;
