@@ -229,6 +229,16 @@ LASSO_RAN_RB = {2: 0x4000, 3: 0x8000, 4: 0x10000, 6: 0x20000}             # KP_L
 SYMM_BY_SHAPE, SYMM_SMALL, SYMM_TILED_RB = 0, 1, 10                       # `variant` of kp_symm_product
 SYMM_RAN_SMALL, SYMM_RAN_NAIVE, SYMM_RAN_TILED = 1, 2, 1000               # its `ran`: tiled = 1000 + 10 RA + RB
 
+# the TN product of the wide path alone (include/koopman_hip_tn.h)
+TN_SIGNATURES = {
+    "kp_tn_product": (C.c_int, [vp, c_dp, C.c_int64, c_dp, C.c_int64, C.c_int, C.c_int, C.c_int, c_dp, C.c_int64, C.c_double, C.c_double,
+                                C.c_int, C.c_int, c_dp, c_dp, C.c_int, C.c_int, c_ip]),
+}
+TN_MISALIGN, TN_SAME, TN_MIRROR = 0x1, 0x2, 0x4                           # `flags` of kp_tn_product
+TN_RAN_FORM, TN_RAN_VEC = 1000, 100                                       # its `ran`: 1000 form + 100 vec + splits
+TN_FORM_SMALL = 4                                                         # the 64 x 64 form (M <= 64)
+TN_SHAPES = ((128, 64), (128, 96), (256, 96), (192, 128))                 # `form` 0 ... 3: tng_shapes() of csrc/kp_tn_gemm.h
+
 _lib = None
 
 
@@ -241,7 +251,8 @@ def lib():
                           "(make -C koopman-realizations_amd/csrc)")
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in (SIGNATURES | NMPC_SIGNATURES | OBSERVER_SIGNATURES | CT_SIGNATURES | ARM_SIGNATURES
-                                   | RSYS_SIGNATURES | VALIDATE_SIGNATURES | HORIZON_SIGNATURES | SIM_SIGNATURES | SPECTRUM_SIGNATURES | LASSO_SIGNATURES).items():
+                                   | RSYS_SIGNATURES | VALIDATE_SIGNATURES | HORIZON_SIGNATURES | SIM_SIGNATURES | SPECTRUM_SIGNATURES | LASSO_SIGNATURES
+                                   | TN_SIGNATURES).items():
             fn = getattr(l, name)
             fn.restype, fn.argtypes = res, args
         _lib = l

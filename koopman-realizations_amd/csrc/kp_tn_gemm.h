@@ -277,14 +277,16 @@ static inline int64_t tng_count_tiles(int M, int N, int tm, int tn, int tri) {
     for (int c = 0; c < nct; ++c) cnt += r * tm <= c * tn + tn - 1 ? 1 : 0;
   return cnt;
 }
+// ran (or nullptr): + 100 when the 16-byte staging kernel is the one launched (kp_tn_gemm, include/koopman_hip_tn.h)
 template <int RA, int RB, int NW = 4, bool VEC = false>
-static hipError_t tng_launch_cfg(hipStream_t st, TngArgs g) {
+static hipError_t tng_launch_cfg(hipStream_t st, TngArgs g, int* ran = nullptr) {
   using Cfg = TngCfg<RA, RB, NW>;
   if constexpr (!VEC && RA % 2 == 0 && Cfg::PB % 2 == 0) {
     static const bool no_vec = getenv("KP_TNG_NOVEC") != nullptr;       // (A/B measurements)
     if (!no_vec && ((uintptr_t)g.A % 16) == 0 && ((uintptr_t)g.B % 16) == 0 && g.lda % 2 == 0 && g.ldb % 2 == 0)
-      return tng_launch_cfg<RA, RB, NW, true>(st, g);
+      return tng_launch_cfg<RA, RB, NW, true>(st, g, ran);
   }
+  if (ran && VEC) *ran += 100;
   static bool attr_set[32] = {};
   int dev = 0;
   (void)hipGetDevice(&dev);
@@ -384,8 +386,11 @@ static inline int tng_pick_splits(int M, int N, int K, int tri, int slots) {
 
 // P (or nullptr): room for nsplit * M * N doubles when nsplit > 1.
 // wa, wb (or nullptr): row weights, see TngArgs.
+// form: -1 as tng_pick_shape picks, 0 ... 3 that index of tng_shapes() (M <= 64 always takes the 64 x 64 form).
+// ran (or nullptr): 1000 x form (0 ... 3, 4 the 64 x 64 form) + 100 x (16-byte staging) + splits that run (include/koopman_hip_tn.h).
 static inline hipError_t kp_tn_gemm(hipStream_t st, const double* A, int64_t lda, const double* B, int64_t ldb, int M, int N, int K, double* C, int64_t ldc,
-                                    double alpha, double beta, int tri, int nsplit, double* P, const double* wa = nullptr, const double* wb = nullptr) {
+                                    double alpha, double beta, int tri, int nsplit, double* P, const double* wa = nullptr, const double* wb = nullptr,
+                                    int form = -1, int* ran = nullptr) {
   if (M <= 0 || N <= 0) return hipSuccess;
   // tile rows are addressed by 32-bit byte offsets from the tile's base
   if ((uint64_t)256 * (uint64_t)(lda > ldb ? lda : ldb) * 8u + (uint64_t)K * 8u >= (1ull << 32)) return hipErrorInvalidValue;
@@ -402,11 +407,13 @@ static inline hipError_t kp_tn_gemm(hipStream_t st, const double* A, int64_t lda
   g.tri = tri;
   g.alpha = alpha; g.beta = beta;
   g.wa = wa; g.wb = wb;
-  if (M <= 64) return tng_launch_cfg<4, 4>(st, g);
-  switch (tng_pick_shape(M, N, g.nsplit, tri)) {
-    case 3: return tng_launch_cfg<6, 8, 8>(st, g);
-    case 2: return tng_launch_cfg<8, 6, 8>(st, g);
-    case 1: return tng_launch_cfg<8, 6>(st, g);
-    default: return tng_launch_cfg<8, 4>(st, g);
+  const int f = M <= 64 ? 4 : form >= 0 && form < TNG_NSHAPES ? form : tng_pick_shape(M, N, g.nsplit, tri);
+  if (ran) *ran = 1000 * f + g.nsplit;
+  switch (f) {
+    case 4: return tng_launch_cfg<4, 4>(st, g, ran);
+    case 3: return tng_launch_cfg<6, 8, 8>(st, g, ran);
+    case 2: return tng_launch_cfg<8, 6, 8>(st, g, ran);
+    case 1: return tng_launch_cfg<8, 6>(st, g, ran);
+    default: return tng_launch_cfg<8, 4>(st, g, ran);
   }
 }

@@ -14,7 +14,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <string>
 
+#include "koopman_hip_tn.h"
 #include "kp_internal.h"
 #include "kp_tn_gemm.h"
 
@@ -114,5 +116,54 @@ int kp_gram_wide_launch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* 
     return 2.0 * tm * tn * cnt;
   };
   ctx->timers[10] = npair * (tiles(1, nsplit_g) + tiles(0, nsplit_c));
+  return KP_OK;
+}
+
+// The TN product alone (include/koopman_hip_tn.h): host operands in, one kp_tn_gemm on the context's stream, all of C back.
+// One workspace slot holds A, B, C, the split partials and the weights, each from a 256-byte boundary (A and B 8 bytes
+// past theirs with KP_TN_MISALIGN).
+extern "C" int kp_tn_product(kp_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, int M, int N, int K,
+                             double* C, int64_t ldc, double alpha, double beta, int tri, int nsplit,
+                             const double* wa, const double* wb, int form, int flags, int* ran) {
+  const bool same = (flags & KP_TN_SAME) != 0, mirror = (flags & KP_TN_MIRROR) != 0;
+  if (!ctx) return KP_ERR_ARG;
+  if (!A || !C || (!B && !same) || M < 1 || N < 1 || K < 1 || lda < K || (!same && ldb < K) || ldc < M || form < -1 || form >= TNG_NSHAPES ||
+      (flags & ~(KP_TN_MISALIGN | KP_TN_SAME | KP_TN_MIRROR)) != 0 || ((same || mirror) && N != M) || (same && ldb != lda) || nsplit < 1 || nsplit > 64)
+    return ctx->fail(KP_ERR_ARG, "kp_tn_product: bad argument");
+  KP_HIP(ctx, hipSetDevice(ctx->device));
+  auto pad = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t mis = (flags & KP_TN_MISALIGN) ? 8 : 0;
+  const size_t nA = (size_t)(M - 1) * lda + K, nB = same ? 0 : (size_t)(N - 1) * ldb + K;      // doubles the host arrays hold for sure
+  const size_t bA = pad(((size_t)M * lda + 1) * 8), bB = same ? 0 : pad(((size_t)N * ldb + 1) * 8), bC = pad((size_t)N * ldc * 8);
+  const size_t bP = nsplit > 1 ? pad((size_t)nsplit * M * N * 8) : 0, bW = pad((size_t)K * 8);
+  char* ws = (char*)ctx->workspace(17, bA + bB + bC + bP + 2 * bW);
+  if (!ws) return ctx->fail(KP_ERR_HIP, "kp_tn_product: out of device memory");
+  double* dA = (double*)(ws + mis);
+  double* dB = same ? dA : (double*)(ws + bA + mis);
+  double* dC = (double*)(ws + bA + bB);
+  double* dP = nsplit > 1 ? (double*)(ws + bA + bB + bC) : nullptr;
+  double* dwa = wa ? (double*)(ws + bA + bB + bC + bP) : nullptr;
+  double* dwb = wb ? (double*)(ws + bA + bB + bC + bP + bW) : nullptr;
+  hipStream_t s = ctx->stream;
+  KP_HIP(ctx, hipMemsetAsync(ws, 0xff, bA + bB, s));
+  KP_HIP(ctx, hipMemcpyAsync(dA, A, nA * 8, hipMemcpyHostToDevice, s));
+  if (!same) KP_HIP(ctx, hipMemcpyAsync(dB, B, nB * 8, hipMemcpyHostToDevice, s));
+  KP_HIP(ctx, hipMemcpyAsync(dC, C, (size_t)N * ldc * 8, hipMemcpyHostToDevice, s));
+  if (dP) KP_HIP(ctx, hipMemsetAsync(dP, 0xff, bP, s));
+  if (dwa) KP_HIP(ctx, hipMemcpyAsync(dwa, wa, (size_t)K * 8, hipMemcpyHostToDevice, s));
+  if (dwb) KP_HIP(ctx, hipMemcpyAsync(dwb, wb, (size_t)K * 8, hipMemcpyHostToDevice, s));
+  int r = 0;
+  hipError_t e = kp_tn_gemm(s, dA, lda, dB, ldb, M, N, K, dC, ldc, alpha, beta, tri, nsplit, dP, dwa, dwb, form, &r);
+  if (e == hipSuccess && mirror) {
+    hipLaunchKernelGGL(kp_mirror_upper_kernel, dim3((M + 15) / 16, (M + 15) / 16), dim3(256), 0, s, dC, M, ldc);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(s);          // the uploads read the caller's arrays
+    return ctx->fail(KP_ERR_HIP, std::string("kp_tn_product: kp_tn_gemm: ") + hipGetErrorString(e));
+  }
+  KP_HIP(ctx, hipMemcpyAsync(C, dC, (size_t)N * ldc * 8, hipMemcpyDeviceToHost, s));
+  KP_HIP(ctx, hipStreamSynchronize(s));
+  if (ran) *ran = r;
   return KP_OK;
 }

@@ -175,6 +175,30 @@ class Context:
         F.check(F.lib().kp_symm_product(self._h, F.dptr(G), F.dptr(X), W, nc, int(variant), F.dptr(Cm), C.byref(ran)), self._h)
         return Cm, ran.value
 
+    def tn_product(self, A, B, Cm, K=None, alpha=1.0, beta=0.0, tri=0, nsplit=1, wa=None, wb=None, form=-1, flags=0):
+        """kp_tn_product: Cm = beta Cm + alpha (diag(wa wb) A[:K])' B[:K] with the TN product of the wide path alone.  A (lda, M)
+        and B (ldb, N; None with F.TN_SAME) are taken with their leading dimensions as they are, rows K and beyond are padding
+        (K defaults to lda); Cm (ldc, N) is a column-major float64 array that is uploaded whole and overwritten IN PLACE with all
+        the device buffer holds afterwards, rows beyond M included.  Returns ran = F.TN_RAN_FORM form + F.TN_RAN_VEC vec + the
+        splits that ran."""
+        A = F.fcol(A)
+        B = None if B is None else F.fcol(B)
+        if not (isinstance(Cm, np.ndarray) and Cm.dtype == np.float64 and Cm.ndim == 2 and Cm.flags.f_contiguous and Cm.flags.writeable):
+            raise ValueError("tn_product: Cm must be a writeable column-major float64 matrix (it is overwritten in place)")
+        lda, M = A.shape
+        ldb, N = (lda, M) if B is None else B.shape
+        if Cm.shape[1] != N:
+            raise ValueError("tn_product: Cm must have as many columns as B")
+        K = lda if K is None else int(K)
+        wa = None if wa is None else np.ascontiguousarray(wa, dtype=np.float64)
+        wb = None if wb is None else np.ascontiguousarray(wb, dtype=np.float64)
+        if any(w is not None and w.shape != (K,) for w in (wa, wb)):
+            raise ValueError("tn_product: wa and wb must have length K")
+        ran = C.c_int()
+        F.check(F.lib().kp_tn_product(self._h, F.dptr(A), lda, F.dptr(B), ldb, M, N, K, F.dptr(Cm), Cm.shape[0], float(alpha), float(beta),
+                                      int(tri), int(nsplit), F.dptr(wa), F.dptr(wb), int(form), int(flags), C.byref(ran)), self._h)
+        return ran.value
+
     def fit_batch(self, basis, snaps, nb):
         """Least-squares fits of nb systems that share one dictionary (W <= 16): `snaps` holds the merged snapshot
         pairs, nb x Ns_each rows.  Returns K, G, C as (nb, W, W) arrays and the status vector."""
