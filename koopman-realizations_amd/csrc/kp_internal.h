@@ -9,12 +9,13 @@
 #include <vector>
 
 #include "koopman_hip.h"
+#include "kp_col_desc.h"   // COL_* kinds and ColDesc (HIP-free)
 
 #define KP_MAX_VARS 32
 #define KP_GRAM_GROUP_MAX 8   // pipelined fits that may share one Gram launch (kp_fit.hip: KP_GRAM_GROUP)
 
 void kp_set_global_error(const std::string& s);
-// kp_batch.hip: the device blocks of a new kp_traj (0 Y, 1 U, 2 Yv, 3 Uv), marked as put - the caller fills them on the
+// kp_traj.hip: the device blocks of a new kp_traj (0 Y, 1 U, 2 Yv, 3 Uv), marked as put - the caller fills them on the
 // context's stream, then kp_traj_finish scales them as for an upload
 void kp_traj_device_blocks(kp_traj* t, double** blocks);
 struct kp_comm_state;   // RCCL communicator of a multi-process run (kp_comm.hip)
@@ -91,7 +92,7 @@ struct kp_ctx {
   int64_t hbm_bytes = 0;
   std::string name;
   mutable std::string err;
-  double timers[28] = {0};            // (27: bit mask of the kernels the iteration loop of the most recent lasso batch launched, not a time; kp_lasso.hip; 26: where the tiles of the last Kronecker Gram launch had their barrier, 1 in front of the last quad steps, 0 behind the last one; kp_gram3.hip; 25: 1000 x model staged + the tile width of the most recent kp_validate_horizon, not a time; 24: its two kernels, ms; kp_validate_horizon.hip; 23: the regime of the most recent kp_eig, not a time; 22: its kernel, ms; kp_eig_general.hip; 21: kernel of the most recent kp_nmpc_simulate, ms; kp_nmpc.hip; 20: the lift order of the last Kronecker Gram launch, 1 the slot table, 0 tid + 256 j; kp_gram3.hip; 19: kernel of the most recent kp_mpc_simulate, ms; kp_mpc.hip; 18: entry, workgroup order and copies of the most recent batched solve, not a time; kp_solve.hip; 17: which panel kernel and substitution form the most recent rank-revealing solve ran, not a time; kp_pivchol.hip; 16: power-table entries per raw value written by the in-loop build of the last Kronecker Gram launch, 3 or 4; 15: jobs of the last Kronecker Gram launch's plan that span two A groups; kp_gram3.hip; 12: the group size of the Gram queue, 13: fits served by the launches of timer 7; kp_fit.hip; 14: kernel code of the most recent sweep call, not a time; kp_batch.hip)
+  double timers[28] = {0};            // (27: bit mask of the kernels the iteration loop of the most recent lasso batch launched, not a time; kp_lasso.hip; 26: where the tiles of the last Kronecker Gram launch had their barrier, 1 in front of the last quad steps, 0 behind the last one; kp_gram3.hip; 25: 1000 x model staged + the tile width of the most recent kp_validate_horizon, not a time; 24: its two kernels, ms; kp_validate_horizon.hip; 23: the regime of the most recent kp_eig, not a time; 22: its kernel, ms; kp_eig_general.hip; 21: kernel of the most recent kp_nmpc_simulate, ms; kp_nmpc.hip; 20: the lift order of the last Kronecker Gram launch, 1 the slot table, 0 tid + 256 j; kp_gram3.hip; 19: kernel of the most recent kp_mpc_simulate, ms; kp_mpc.hip; 18: entry, workgroup order and copies of the most recent batched solve, not a time; kp_solve.hip; 17: which panel kernel and substitution form the most recent rank-revealing solve ran, not a time; kp_pivchol.hip; 16: power-table entries per raw value written by the in-loop build of the last Kronecker Gram launch, 3 or 4; 15: jobs of the last Kronecker Gram launch's plan that span two A groups; kp_gram3.hip; 12: the group size of the Gram queue, 13: fits served by the launches of timer 7; kp_fit.hip; 14: kernel code of the most recent sweep call, not a time; kp_sweep.hip, kp_sweep_gram.hip)
   double gram_flops_per_pair = 0;
   // growable device workspaces
   void* ws[21] = {nullptr};     // slot 8: staging of the collectives, 9: rank-revealing solve, 10 / 11: Grams of the shadow dictionary of a dim_red fit, their half-transformed form
@@ -123,18 +124,6 @@ struct kp_ctx {
     if (_e != hipSuccess)                                                                  \
       return (ctx)->fail(KP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));   \
   } while (0)
-
-// Column kinds of the full basis (device table, one entry per full-basis column)
-enum : int { COL_VAR = 0, COL_MONO = 1, COL_FOURIER = 2, COL_GAUSS = 3, COL_CONST = 4, COL_HERMITE = 5, COL_FSPARSE = 6 };
-
-struct ColDesc {
-  int32_t kind;
-  int32_t arg;  // VAR: variable index; MONO/HERMITE: row in exps; FSPARSE: first of two rows in exps (sin, cos
-                // multipliers); FOURIER: mixed-radix index (>=1); GAUSS: centre
-  int32_t aux;  // FOURIER: degree; MONO with <= 8 variables (kp_basis_create): exponent bytes of variables 0-3
-  int32_t pad;  // MONO with <= 8 variables: exponent bytes of variables 4-7; FOURIER (<= 8 variables, degree <= 7): the digits of the
-                // mixed-radix index, four bits per variable (0: not packed)
-};
 
 // Device view of a dictionary, passed by value to kernels.
 struct BasisDev {
@@ -223,6 +212,21 @@ int kp_dev_alloc_copy(kp_ctx* ctx, double** dst, const double* src, size_t n);
 void kp_stage_destroy(kp_ctx* ctx);
 void kp_host_free_all(kp_ctx* ctx);
 void kp_traj_pool_free(kp_ctx* ctx);
+// ---- launchers of the W <= 16 kernels (kp_small_tile.h) that another file launches, on ctx->stream; the caller checks hipGetLastError ----
+struct TrajView;
+// kp_small_fit_kernel (kp_small_fit.hip), nb systems of Ns rows: snapshots from alpha / beta / u (Ns_total rows in all) or, with
+// tv.Y set, from the trajectories.  Reads KP_BATCH_REFINE; returns whether the power-table recipes lift.
+bool kp_small_fit_launch(kp_ctx* ctx, const kp_basis* basis, int nb, const double* alpha, const double* beta, const double* u, int64_t Ns_total,
+                         int Ns, const TrajView& tv, double* dK, double* dG, double* dC, int* dS);
+// kp_small_project_kernel (kp_small_fit.hip): the M-projection of nb linear models; dM and dS may be nullptr
+void kp_small_project_launch(kp_ctx* ctx, int nb, const double* dK, const double* dG, const double* dC, int N, int m, double* dA, double* dB,
+                             double* dM, int* dS);
+// The Gram pass of the nested sweep (kp_sweep_gram.hip): picks the kernel (KP_SWEEP_GRAM_OLD, KP_SWEEP_GRAM_V1), records ctx->ev0 and
+// launches it; timers[10] for a matrix-pipe kernel, *code = the part 1000 G + 100 F + 10 U of the timer-14 code (koopman_hip.h)
+int kp_sweep_gram_launch(kp_ctx* ctx, const kp_traj* traj, const kp_basis* basis, int Ns, bool cheb, double* dGc, double* dCc, double* code);
+// Workspace 6 of kp_sweep_eval_nested (SweepWs in kp_sweep.hip, which kp_sweep_nested_get_K reads K through): Gc | Cc (nb x Wmax x Wmax)
+// | K | G | C | A | B (n_deg x nb x 256 doubles each) | err (n_deg x nb x n) | nb spare status words | status | L1 flags (n_deg x nb
+// ints each) | SweepDeg table | ColDesc table (both 64-byte aligned)
 // Around every launch sequence that reads a snapshot object.  All readers run on ctx->stream, so one wait orders the
 // later ones too.
 inline hipError_t kp_snaps_acquire(const kp_snapshots* s, hipStream_t st) {

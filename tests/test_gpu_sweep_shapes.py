@@ -1,4 +1,4 @@
-"""GPU tests of kp_sweep_eval_nested / kp_sweep_eval (csrc/kp_batch.hip) in every kernel the dictionary can select, beyond the
+"""GPU tests of kp_sweep_eval_nested / kp_sweep_eval (csrc/kp_sweep.hip, kp_sweep_gram.hip) in every kernel the dictionary can select, beyond the
 1-state / 1-input shapes of the benchmark.  Reference: tests/_sweep_reference.py (the oracle for full exponent tables, its
 plain numpy restatement for sparse ones, a long-double rollout of the device's own model).  Every case proves which kernels
 it ran through kp_timer_get(14) = 1000 G + 100 F + 10 U + R (include/koopman_hip.h).
