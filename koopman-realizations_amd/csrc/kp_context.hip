@@ -5,6 +5,7 @@
 #include <mutex>
 
 #include "kp_internal.h"
+#include "kp_lift_plan.h"   // launch plan of kp_lift_kernel, digit packing of fourier columns (HIP-free)
 
 static std::mutex g_err_mu;
 static std::string g_err;
@@ -217,7 +218,7 @@ extern "C" int kp_basis_create(kp_ctx* ctx, const kp_basis_desc* d, kp_basis** o
   if (nvars > KP_MAX_VARS) return ctx->fail(KP_ERR_ARG, "kp_basis_create: too many variables (max 32)");
   std::vector<ColDesc> cols;
   for (int i = 0; i < nvars; ++i) cols.push_back({COL_VAR, i, 0, 0});
-  int n_mono = 0, n_gauss = 0, max_deg = 1, fourier_deg = 0;
+  int n_mono = 0, n_gauss = 0, max_deg = 1;
   for (int b = 0; b < d->n_blocks; ++b) {
     int cnt = d->block_count[b];
     if (cnt < 0) return ctx->fail(KP_ERR_ARG, "kp_basis_create: negative block count");
@@ -241,22 +242,7 @@ extern "C" int kp_basis_create(kp_ctx* ctx, const kp_basis_desc* d, kp_basis** o
         if (cnt < 1) return ctx->fail(KP_ERR_ARG, "kp_basis_create: fourier degree < 1");
         double nf = std::pow((double)(2 * cnt + 1), (double)nvars);
         if (nf > 1e6) return ctx->fail(KP_ERR_ARG, "kp_basis_create: fourier block too large");
-        int total = (int)std::llround(nf);
-        for (int i = 1; i < total; ++i) {
-          // the digits of the mixed-radix index (digit of variable v = harmonic of x_v: 0 none, 2j - 1 cos, 2j sin) packed four
-          // bits each into `pad` when they fit: the lift kernel then shifts instead of dividing - twelve 32-bit integer
-          // divisions per function and point were ~200 of the ~300 instructions of a fourier value
-          uint32_t pk = 0;
-          if (nvars <= 8 && 2 * cnt + 1 <= 16) {
-            int idx = i;
-            for (int v = nvars - 1; v >= 0; --v) {
-              pk |= (uint32_t)(idx % (2 * cnt + 1)) << (4 * v);
-              idx /= 2 * cnt + 1;
-            }
-          }
-          cols.push_back({COL_FOURIER, i, cnt, (int32_t)pk});
-        }
-        fourier_deg = fourier_deg == 0 ? cnt : (fourier_deg == cnt ? cnt : -1);   // (blocks of different degrees: generic evaluation)
+        lift_fourier_append(cols, cnt, nvars, (int)std::llround(nf));      // digits packed into `pad` where they fit (kp_lift_plan.h)
         break;
       }
       case KP_BLOCK_HERMITE:
@@ -282,10 +268,7 @@ extern "C" int kp_basis_create(kp_ctx* ctx, const kp_basis_desc* d, kp_basis** o
   kp_basis* b = new kp_basis();
   b->ctx = ctx;
   b->max_degree = max_deg;
-  b->fourier_degree = (fourier_deg > 0 && fourier_deg <= 8) ? fourier_deg : 0;
-  b->pure_fourier = b->fourier_degree > 0 && (int)cols.size() > nvars;
-  for (size_t c = (size_t)nvars; c < cols.size() && b->pure_fourier; ++c)
-    b->pure_fourier = cols[c].kind == COL_CONST || (cols[c].kind == COL_FOURIER && cols[c].pad != 0 && cols[c].aux == b->fourier_degree);
+  lift_fourier_flags(cols, nvars, &b->fourier_degree, &b->pure_fourier);
   // recipes of the fused Gram kernel's fast lift: column = product of <= 4 entries x_v^e of a
   // power table, id = v*D + (e-1), 255 = the constant 1
   {
@@ -616,16 +599,11 @@ int kp_lift_dev_ld(kp_ctx* ctx, const kp_basis* basis, int what, const double* d
                    int64_t ldo) {
   const BasisDev& b = basis->dev;
   const int fdeg = basis->fourier_degree;
-  const size_t per_point = (size_t)(b.nvars + (b.m > 0 ? b.m : 1) + b.nvars * (fdeg > 0 ? 2 * fdeg + 1 : 0) + (b.k_pcs ? b.nfull : 0)) * 8;
-  // 64 points per workgroup when that still gives every CU several workgroups (the kernel is bound by instruction issue: one
-  // workgroup per CU is one wave per SIMD, a quarter of what a SIMD can issue), else 16
-  const int ncu_ = ctx->num_cu > 0 ? ctx->num_cu : 256;
-  const int lt = (per_point * 64 <= 160 * 1024 && rows >= (int64_t)64 * 4 * ncu_) ? 64 : 16;
-  size_t lds = per_point * lt;
-  if (lds > 160 * 1024) return ctx->fail(KP_ERR_ARG, "kp_lift: dictionary too large for the LDS staging of the pcs projection");
-  int stage_cols = lds + (size_t)b.nfull * sizeof(ColDesc) <= 160 * 1024 ? 1 : 0;
-  if (stage_cols) lds += (size_t)b.nfull * sizeof(ColDesc);
-  if (stage_cols && basis->pure_fourier && fdeg > 0 && b.nvars <= 8) stage_cols |= 2;      // bit 1: the fourier-only loop of the kernel
+  // points per workgroup, LDS bytes, stage_cols (bit 0: descriptors in LDS, bit 1: the fourier-only loop) - kp_lift_plan.h
+  const LiftPlan plan = lift_plan_build(b.nvars, b.m, b.nfull, b.k_pcs, fdeg, basis->pure_fourier, rows, ctx->num_cu);
+  if (plan.refusal) return ctx->fail(KP_ERR_ARG, plan.refusal);
+  const int lt = plan.lt, stage_cols = plan.stage_cols;
+  const size_t lds = plan.lds;
   static KpLdsCache c64, c16;
   const int64_t nblk = (rows + lt - 1) / lt;
   if (lt == 64) {
