@@ -58,76 +58,19 @@
 #ifndef KP_RAW_STEP
 #define KP_RAW_STEP 1   // MFMA step of a tile behind which the raw loads of the tile after next are issued
 #endif
-#define KT3 8     // snapshots per LDS tile (two k-steps)
-#define NF3 3     // single-variable powers per column (recipes with 4 factors use the general monomial kernel)
-// LDS row (doubles): psi_x [0,96) | psi_y [96,192) | zero group [192,196) | weights [196,208) | scratch [208,240)
-#define RS3 240   // = 16 mod 32: the four k-rows of an MFMA operand read hit disjoint banks
-#define YOFF3 96
-#define ZOFF3 192
-#define WOFF3 196
-#define SOFF3 208
-#define NIDMAX3 144                 // power-table entries per snapshot (2 x 16 rows x 4 powers + the constant row's 4 fit)
-#define PST3 10                     // doubles per power-table entry: KT3 snapshots + 2 of padding, so that the 16-byte reads of
-                                    // 64 lanes with arbitrary ids spread over all banks (a stride of 8 puts them on 4 groups)
-#define POWBUF3 (PST3 * NIDMAX3)    // doubles per power-table buffer
-#define PSIBUF3 (KT3 * RS3)         // doubles per Psi buffer
-#define PSI03 (2 * POWBUF3)         // LDS: pow[2] | psi[2]
-#define LDS3_DOUBLES (PSI03 + 2 * PSIBUF3)
-// dim_red dictionaries: the projection matrix lives behind the Psi buffers as [column tile of 16 PCs][full column][16]
-// (row stride 16 doubles: the two full columns a 32-lane group reads sit on disjoint banks), at most 32 PCs
-#define PCS03 LDS3_DOUBLES
-#define PCSMAX3 32
-#define LDS3_PCS_DOUBLES (2 * YOFF3 * 16)
-// fourier / gaussian dictionaries (EXT): the per-variable table also holds cos / sin(2 pi j x) behind the powers, and one
-// entry per (side, gaussian centre) behind the constant; the centres live in LDS where the projection matrix would
-#define GC03 LDS3_DOUBLES
-#define GAUSSMAX3 32                // centres (2 sides x 32 x KT3 values per tile = two items per thread)
+// (the LDS layout constants KT3 .. LDS3_GAUSS_DOUBLES and gram3_tile_timing: kp_gram3_launch.h, shared with the launch decisions)
 #ifndef KP_PCS_REGS
 #define KP_PCS_REGS 24                 // k-steps of the pcs projection whose matrix operand stays in registers (<= 96 full columns)
 #endif
-#define GNZMAX3 8                   // state variables of a gaussian dictionary
-#define LDS3_GAUSS_DOUBLES (GAUSSMAX3 * GNZMAX3)
 
 #include "kp_gram3_args.h"
 #include "kp_gram3_cover.h"
 #include "kp_gram3_lift.h"
+#include "kp_gram3_launch.h"
 
 // the constant row of the in-loop power table "loads" its 1.0 like the raw rows load their values (kp_gram3_kernel, INL); not
 // `const`: a pointer that may be this or a kernel argument must stay a GLOBAL pointer (constant address space: flat loads)
 __device__ double kp_gram3_ones[KT3] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
-
-// EB (the early tile barrier of kp_gram3_kernel): where a tile of NQ quads per wave places its barrier and how it
-// times the lift's three chunks.  One function for the kernel and for the launcher, so that the timer slot tells what ran.
-#ifndef KP_GRAM3_EB_BEHIND
-#define KP_GRAM3_EB_BEHIND 0        // quad steps of a tile that run behind its barrier; 0: as many as B operands are requested ahead
-#endif
-struct Gram3TileTiming {
-  int pf;        // B operands are requested this many quad steps ahead
-  int sp, lag;   // lift chunk i: table reads at step i sp, multiplies and stores at step i sp + lag
-  int bs;        // step whose end holds the tile's barrier; -1: the barrier stays behind the last step (today's placement)
-};
-constexpr Gram3TileTiming gram3_tile_timing(int nq, bool lo, bool eb) {
-  const int nstep = (KT3 / 4) * nq, nch = 3;
-  const int pf_ahead = lo ? 2 : 3;                      // (2 and 4 steps ahead measured the same; LO: four registers for the lift's addresses)
-  const int pf = nstep < pf_ahead ? nstep : pf_ahead;
-  const int sp = nstep / nch > 0 ? nstep / nch : 1;
-  const int lag = sp / 2 > 0 ? sp / 2 : 1;
-  // (with the ordered lift only: the order e = tid + 256 j requests B operands three steps ahead and does not pin its twelve
-  // lift addresses - with operands carried across the tile boundary its NQ = 6 loops hold 14 to 16 scratch accesses each)
-  if (eb && lo) {
-    // the barrier step: every operand read of the tile is issued at or before it (B operands run pf steps ahead) unless fewer
-    // steps are asked to stay behind it; it must lie in the tile's last k-step (the A fragments and weights of every k-step are
-    // requested by then) and at or behind the last lift store.  The chunks move together - the largest spacing of at least
-    // two steps that fits, the lag kept - and where none fits the placement is today's: a compile-time matter, never a hazard.
-    const int behind = KP_GRAM3_EB_BEHIND > 0 && KP_GRAM3_EB_BEHIND < pf ? KP_GRAM3_EB_BEHIND : pf;
-    const int bs = nstep - 1 - behind;
-    for (int s = sp; s >= 2; --s) {
-      const int l = lag < s ? lag : s;
-      if (bs >= (KT3 / 4 - 1) * nq && (nch - 1) * s + l <= bs) return {pf, s, l, bs};
-    }
-  }
-  return {pf, sp, lag, -1};
-}
 
 // PCS: econ lift through a projection matrix (dim_red dictionaries)
 // EXT: fourier (def_fourierLift, Ksysid.m:694-731) and gaussian (def_gaussianLift, :790-817) blocks through the same table
@@ -986,7 +929,7 @@ static int make_plan3(kp_ctx* ctx, int N, int nwt, int nq_cap, kp_gram3_plan** o
 }
 
 template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool P3 = false, bool LO = false, bool EB = false>
-static hipError_t launch3d(const Gram3Args& a, int grid, size_t lds, hipStream_t st) {
+static hipError_t launch3(const Gram3Args& a, int grid, size_t lds, hipStream_t st) {
   static KpLdsCache lds_cache;
   {
     const size_t lds_max = (size_t)(LDS3_DOUBLES + (PCS ? LDS3_PCS_DOUBLES : 0) + (EXT ? LDS3_GAUSS_DOUBLES : 0)) * sizeof(double);
@@ -997,86 +940,67 @@ static hipError_t launch3d(const Gram3Args& a, int grid, size_t lds, hipStream_t
   return hipGetLastError();
 }
 
-template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false, bool P3 = false, bool LO = false>
-static hipError_t launch3c(const Gram3Args& a, int grid, size_t lds, hipStream_t st) {
-  // the early tile barrier, in the in-kernel-lift monomial kernel whose tile has the room (gram3_launch_n sets eb only there)
-  if constexpr (!PCS && !EXT && !PRE && gram3_tile_timing(NQ, LO, true).bs >= 0) {
-    if (a.eb) return launch3d<NQ, BM, PCS, EXT, PRE, P3, LO, true>(a, grid, lds, st);
+// From the form of a launch (gram3_form, kp_gram3_launch.h) to its instantiation - the one place that names them.  The guards
+// bound the set: PCS to NQ <= 4 (more quads per wave spill once the projection is inlined; plans of dim_red dictionaries stay
+// below), P3 / LO to the monomial form, EB to the tiles that have the room - which only a tile of the ordered lift has.
+template <int NQ, int BM>
+static hipError_t gram3_dispatch_at(const Gram3Form& f, const Gram3Args& a, int grid, size_t lds, hipStream_t st) {
+  static_assert(gram3_tile_timing(NQ, false, true).bs < 0, "early tile barrier: with the ordered lift only");
+  switch (f.kind) {
+    case GRAM3_PRE: return launch3<NQ, BM, false, false, true>(a, grid, lds, st);
+    case GRAM3_PCS:
+      if constexpr (NQ <= 4) return launch3<NQ, BM, true>(a, grid, lds, st);
+      else return hipErrorInvalidValue;
+    case GRAM3_EXT: return launch3<NQ, BM, false, true>(a, grid, lds, st);
+    case GRAM3_MONO: break;
   }
-  return launch3d<NQ, BM, PCS, EXT, PRE, P3, LO, false>(a, grid, lds, st);
-}
-
-template <int NQ, int BM, bool PCS, bool EXT = false, bool PRE = false>
-static hipError_t launch3b(const Gram3Args& a, int grid, size_t lds, hipStream_t st) {
-  if constexpr (!PCS && !EXT && !PRE) {
-    // the lift's jobs in the slots of the dictionary's table (gram3_launch_n sets lift only in this form)
-    if (a.lift) return a.pow3 ? launch3c<NQ, BM, false, false, false, true, true>(a, grid, lds, st)
-                              : launch3c<NQ, BM, false, false, false, false, true>(a, grid, lds, st);
-    // no fourth power in the dictionary: the three-entry table (gram3_launch_n sets pow3 only in this form)
-    if (a.pow3) return launch3c<NQ, BM, false, false, false, true>(a, grid, lds, st);
+  if constexpr (gram3_tile_timing(NQ, true, true).bs >= 0) {
+    if (f.eb) return f.p3 ? launch3<NQ, BM, false, false, false, true, true, true>(a, grid, lds, st) : launch3<NQ, BM, false, false, false, false, true, true>(a, grid, lds, st);
   }
-  return launch3c<NQ, BM, PCS, EXT, PRE>(a, grid, lds, st);
+  if (f.lo) return f.p3 ? launch3<NQ, BM, false, false, false, true, true>(a, grid, lds, st) : launch3<NQ, BM, false, false, false, false, true>(a, grid, lds, st);
+  return f.p3 ? launch3<NQ, BM, false, false, false, true>(a, grid, lds, st) : launch3<NQ, BM, false>(a, grid, lds, st);
 }
 
 template <int NQ>
-static hipError_t launch3(const Gram3Args& a, int bm, int grid, size_t lds, hipStream_t st) {
-  if (a.pre) {                           // dim_red dictionary, econ lift done by kp_gram3_prelift_kernel
-    switch (bm) {
-      case 1: return launch3b<NQ, 1, false, false, true>(a, grid, lds, st);
-      case 2: return launch3b<NQ, 2, false, false, true>(a, grid, lds, st);
-      default: return launch3b<NQ, 3, false, false, true>(a, grid, lds, st);
-    }
-  }
-  if (a.pcs) {
-    if constexpr (NQ <= 4) {             // more quads per wave spill once the projection is inlined (plans of dim_red dictionaries stay below)
-      switch (bm) {
-        case 1: return launch3b<NQ, 1, true>(a, grid, lds, st);
-        case 2: return launch3b<NQ, 2, true>(a, grid, lds, st);
-        default: return launch3b<NQ, 3, true>(a, grid, lds, st);
-      }
-    } else {
-      return hipErrorInvalidValue;
-    }
-  }
-  if (a.df > 0 || a.ng > 0) {            // fourier / gaussian entries in the table
-    switch (bm) {
-      case 1: return launch3b<NQ, 1, false, true>(a, grid, lds, st);
-      case 2: return launch3b<NQ, 2, false, true>(a, grid, lds, st);
-      default: return launch3b<NQ, 3, false, true>(a, grid, lds, st);
-    }
-  }
-  switch (bm) {
-    case 1: return launch3b<NQ, 1, false>(a, grid, lds, st);
-    case 2: return launch3b<NQ, 2, false>(a, grid, lds, st);
-    default: return launch3b<NQ, 3, false>(a, grid, lds, st);
+static hipError_t gram3_dispatch_nq(const Gram3Form& f, const Gram3Args& a, int grid, size_t lds, hipStream_t st) {
+  return f.bm == 1 ? gram3_dispatch_at<NQ, 1>(f, a, grid, lds, st) : f.bm == 2 ? gram3_dispatch_at<NQ, 2>(f, a, grid, lds, st) : gram3_dispatch_at<NQ, 3>(f, a, grid, lds, st);
+}
+
+static hipError_t gram3_dispatch(const Gram3Form& f, const Gram3Args& a, int grid, size_t lds, hipStream_t st) {
+  switch (f.nq) {
+    case 1: return gram3_dispatch_nq<1>(f, a, grid, lds, st);
+    case 2: return gram3_dispatch_nq<2>(f, a, grid, lds, st);
+    case 3: return gram3_dispatch_nq<3>(f, a, grid, lds, st);
+    case 4: return gram3_dispatch_nq<4>(f, a, grid, lds, st);
+    case 5: return gram3_dispatch_nq<5>(f, a, grid, lds, st);
+    default: return gram3_dispatch_nq<6>(f, a, grid, lds, st);
   }
 }
 
-// fourier / gaussian blocks as table entries (EXT kernel): not with a projection, <= GAUSSMAX3 centres, <= GNZMAX3 variables
-static bool gram3_ext(const kp_basis* basis) {
+// The switches of the launch decisions (Gram3Switches).  Read once, when the first question is asked: KP_GRAM3_NO_PRELIFT;
+// KP_GRAM3_PRELIFT_MIN_NS; KP_GRAM3_POW3=0 - the in-loop table build keeps its x^4 entry for every dictionary;
+// KP_GRAM3_LIFT_ORDER=0 - the lift keeps the order e = tid + 256 j for every dictionary; KP_GRAM3_EARLY_BARRIER=0 - every tile
+// keeps its barrier behind the last quad step (the three: A/B runs, tests).  Read at every question: KP_NO_GRAM3_EXT.
+static Gram3Switches gram3_switches() {
+  static const Gram3Switches once = gram3_switches_read(getenv);
+  Gram3Switches s = once;
+  s.ext = !getenv("KP_NO_GRAM3_EXT");
+  return s;
+}
+
+// the facts of a dictionary that the launch decisions read ...
+static Gram3Facts gram3_dict_facts(const kp_basis* basis) {
   const BasisDev& b = basis->dev;
-  return basis->fast_ext && (basis->ext_df > 0 || basis->ext_ng > 0) && b.k_pcs == 0 && basis->ext_ng <= GAUSSMAX3 &&
-         (basis->ext_ng == 0 || b.nzeta <= GNZMAX3) && !getenv("KP_NO_GRAM3_EXT");
+  Gram3Facts f;
+  f.N = b.N; f.m = b.m; f.nfull = b.nfull; f.nzeta = b.nzeta; f.k_pcs = b.k_pcs; f.pow_depth = basis->pow_depth;
+  f.fast = basis->fast; f.fast_ext = basis->fast_ext;
+  f.ext_Dp = basis->ext_Dp; f.ext_df = basis->ext_df; f.ext_ng = basis->ext_ng;
+  return f;
 }
 
-// dim_red dictionaries: econ lift by kp_gram3_prelift_kernel (its power table: 2 x nzeta * depth entries x 256 threads of LDS);
-// fourier / gaussian dictionaries: their table entries once per snapshot by kp_gram3_prelift_ext_kernel (kp_gram3_prelift.hip)
-static bool gram3_prelift(const kp_basis* basis) {
-  static const bool off = getenv("KP_GRAM3_NO_PRELIFT") != nullptr;
-  const BasisDev& b = basis->dev;
-  if (off) return false;
-  if ((b.N + 3) / 4 > 14) return false;               // the tile loader of the PRE kernel moves two 16-byte pieces per thread: 4 (8 G4 + 12) <= 512
-  if (b.k_pcs > 0) return b.k_pcs <= 32 && basis->fast && b.nzeta * basis->pow_depth <= 24;      // (2 x 24 entries x 256 threads: 96 KB of LDS)
-  return gram3_ext(basis) && b.nzeta <= 16 && b.nzeta * (basis->ext_Dp + 2 * basis->ext_df) + basis->ext_ng + 1 <= 64;
-}
+static bool gram3_ext(const kp_basis* basis) { return gram3_ext(gram3_dict_facts(basis), gram3_switches()); }
+static bool gram3_mono(const kp_basis* basis) { return gram3_mono(gram3_dict_facts(basis), gram3_switches()); }
 
-// The forms of kp_gram3_kernel that a launch (pre: it reads a prelift buffer) of a dictionary runs.
-// In-kernel lift (the kernel's INL): the tile loop builds the power table - no fourier / gaussian table entries, no prelift buffer.
-static bool gram3_inl(const kp_basis* basis, bool pre) { return !pre && !gram3_ext(basis); }
-// The in-kernel-lift monomial form (the kernel's GRP): ... and no projection.  P3, LO, EB, the fits that share a launch and the
-// cover plan exist in this form only.  gram3_prelift serves projections and fourier / gaussian tables, so no launch of such a
-// dictionary has a prelift buffer: pre = false asks about the dictionary.
-static bool gram3_inl_mono(const kp_basis* basis, bool pre = false) { return gram3_inl(basis, pre) && basis->dev.k_pcs == 0; }
 
 bool kp_gram3_applicable(const kp_basis* basis) {
   const BasisDev& b = basis->dev;
@@ -1119,7 +1043,7 @@ static bool gram3_onea_on() {
   return on;
 }
 
-// The dictionary's cover plan (kp_gram3_cover.h), built on first use: for the in-kernel-lift monomial form (gram3_inl_mono)
+// The dictionary's cover plan (kp_gram3_cover.h), built on first use: for the in-kernel-lift monomial form (gram3_mono)
 // only - every column a pure monomial, no projection, no fourier / gaussian table entries - and KEPT only when it has
 // fewer jobs (whole workgroups) than the circulant plan and passes its own coverage check on the host.  *out = nullptr: this
 // dictionary runs the circulant plan everywhere.
@@ -1134,7 +1058,7 @@ static int gram3_cover_plan(kp_ctx* ctx, kp_basis* basis, kp_gram3_plan** out) {
     circ.cover_tried = true;
     const BasisDev& b = basis->dev;
     const int N = b.N, NWT = (b.m + 1) * (b.m + 2) / 2;
-    if (!gram3_inl_mono(basis) || !basis->fast || b.nfull != N || (int)basis->h_recipes.size() != N) return KP_OK;
+    if (!gram3_mono(basis) || !basis->fast || b.nfull != N || (int)basis->h_recipes.size() != N) return KP_OK;
     Gram3CoverHost cov;
     if (!gram3_cover_build(basis->h_recipes.data(), N, basis->pow_depth, NWT, 6, &cov) || cov.jobs.njobs >= circ.njobs) return KP_OK;
     if (gram3_onea_on()) {
@@ -1160,24 +1084,6 @@ static int gram3_cover_plan(kp_ctx* ctx, kp_basis* basis, kp_gram3_plan** out) {
   }
   *out = circ.cover;
   return KP_OK;
-}
-
-// KP_GRAM3_POW3=0 (read once): the in-loop table build keeps its x^4 entry for every dictionary (A/B runs, tests)
-static bool gram3_pow3_on() {
-  static const bool on = [] { const char* e = getenv("KP_GRAM3_POW3"); return !e || atoi(e) != 0; }();
-  return on;
-}
-
-// KP_GRAM3_LIFT_ORDER=0 (read once): the lift keeps the order e = tid + 256 j for every dictionary (A/B runs, tests)
-static bool gram3_lift_order_on() {
-  static const bool on = [] { const char* e = getenv("KP_GRAM3_LIFT_ORDER"); return !e || atoi(e) != 0; }();
-  return on;
-}
-
-// KP_GRAM3_EARLY_BARRIER=0 (read once): every tile keeps its barrier behind the last quad step (A/B runs, tests)
-static bool gram3_early_barrier_on() {
-  static const bool on = [] { const char* e = getenv("KP_GRAM3_EARLY_BARRIER"); return !e || atoi(e) != 0; }();
-  return on;
 }
 
 // The dictionary's lift slot table (kp_gram3_lift.h), built and uploaded on first use and kept with its circulant plan;
@@ -1216,18 +1122,23 @@ static int gram3_plan_for(kp_ctx* ctx, kp_basis* basis, bool deferred, kp_gram3_
   return KP_OK;
 }
 
-// workgroup slots of the chip for kp_gram3_kernel
-static int64_t gram3_slots(const kp_ctx* ctx, int* ncu_out = nullptr, int* wgpcu_out = nullptr) {
-  int ncu = ctx->num_cu > 0 ? ctx->num_cu : 256;
-  int wg_per_cu = 2;                                  // __launch_bounds__(256, 2): two workgroups share a CU
-  if (const char* ov = getenv("KP_GRAM3_WGPCU")) wg_per_cu = std::max(1, atoi(ov));
-  if (ncu_out) *ncu_out = ncu;
-  if (wgpcu_out) *wgpcu_out = wg_per_cu;
-  return (int64_t)std::max(8, ncu) * wg_per_cu;
+// ... and of a launch of n fits of Ns snapshots each on `plan` (Gram3Facts, kp_gram3_launch.h).  KP_GRAM3_WGPCU is read at every
+// question.  The dictionary's lift slot table is the launcher's to ask (gram3_lift_table: it builds one).
+static Gram3Facts gram3_facts(const kp_ctx* ctx, const kp_basis* basis, const kp_gram3_plan& plan, int64_t Ns, int n) {
+  Gram3Facts f = gram3_dict_facts(basis);
+  f.nq = plan.nq; f.nsuper = plan.nsuper; f.njobs = plan.njobs; f.two_group_jobs = plan.two_group_jobs;
+  for (const kp_gram3_plan* o : {(const kp_gram3_plan*)basis->plan3, (const kp_gram3_plan*)basis->plan3->cover})
+    if (o && o != &plan) { f.other_nq = o->nq; f.other_nsuper = o->nsuper; f.other_njobs = o->njobs; }
+  f.Ns = Ns;
+  f.n = n;
+  f.num_cu = ctx->num_cu;
+  if (const char* ov = getenv("KP_GRAM3_WGPCU")) f.wg_per_cu = std::max(1, atoi(ov));
+  f.hbm_bytes = ctx->hbm_bytes;
+  return f;
 }
 
 // Fits that may share a Gram launch (kp_fit.hip's queue of pipelined fits): the in-kernel-lift monomial form of kp_gram3_kernel -
-// no projection, no fourier / gaussian table entries, hence no prelift buffer either (gram3_inl_mono); and only while
+// no projection, no fourier / gaussian table entries, hence no prelift buffer either (gram3_mono); and only while
 // a lone launch's splits are shorter than KP_GRAM_GROUP_MAX_KPS tiles.  What sharing saves is a fixed cost per fit (head, write-out
 // and reduction of one accumulator set per wave slot: ~30 us at W = 336, some 15 tile times); what it costs is whole-split
 // granularity, 1 - 1.4 % of the kernel time (a fit of a group of 8 gets 9 of the 73 splits: 504 of 512 slots) - measured at
@@ -1237,89 +1148,64 @@ static int64_t gram3_slots(const kp_ctx* ctx, int* ncu_out = nullptr, int* wgpcu
 bool kp_gram3_groupable(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapshots* s) {
   kp_basis* basis = const_cast<kp_basis*>(basis_c);
   const BasisDev& b = basis->dev;
-  if (!(kp_gram3_applicable(basis) && gram3_inl_mono(basis) && s->nzeta == b.nzeta && s->m == b.m)) return false;
+  if (!(kp_gram3_applicable(basis) && gram3_mono(basis) && s->nzeta == b.nzeta && s->m == b.m)) return false;
   kp_gram3_plan* plan = nullptr;                 // (the plan the queue's launch will run: kp_gram3_launch_group)
   if (gram3_plan_for(ctx, basis, true, &plan) != KP_OK) return false;      // (a plan that cannot be built: the immediate dispatch reports it)
   static const int64_t max_kps = [] { const char* e = getenv("KP_GRAM_GROUP_MAX_KPS"); return e ? (int64_t)atoll(e) : (int64_t)512; }();
-  const int64_t ktiles = (s->Ns + KT3 - 1) / KT3, nsplit = std::max<int64_t>(1, gram3_slots(ctx) / plan->nsuper);
-  return (ktiles + nsplit - 1) / nsplit < max_kps;
+  return gram3_lone_splits_shorter(gram3_facts(ctx, basis, *plan, s->Ns, 1), max_kps);
 }
 
-// ss[0 .. n): the snapshot objects of n fits of one dictionary and ONE snapshot count (n > 1: kp_gram3_groupable); their [G | C]
-// pairs go to GC_dev + f 2 W^2.  The launch is dealt over the fits: nsplit_fit = max(1, (slots / nsuper) / n) splits each.  n = 1
-// is the launch of a single fit, bit for bit.
-static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapshots* const* ss, int n, double* GC_dev, bool cover) {
-  kp_basis* basis = const_cast<kp_basis*>(basis_c);
+// The events around a launch of n fits.  Every event record is a barrier packet the command processor works through between two
+// Gram kernels.  A synchronous launch records ev0 and evp[0] in front of the kernel, evp[1] behind it, ev1 and evp[2] behind the
+// reduction.  The pipelined path (ring_timing) keeps two (kernel start / end) of its ring of event pairs, averaged at
+// kp_synchronize, and those for every 4th launch only (the mean over the ring is what kp_synchronize reports).  A group launch
+// (ring_group: the Gram queue of kp_fit.hip, group size > 1) of several fits is always timed - one event pair per group is the
+// packet rate of every 4th single launch - and so is its reduction (ring_red, timer 6).  A group of ONE keeps the every-4th rule
+// and records no third event: what a single launch recorded before.
+namespace {
+struct Gram3Events {
+  kp_ctx* ctx;
+  bool timed = false;
+  hipEvent_t ev_start = nullptr, ev_end = nullptr, ev_red = nullptr;
+
+  hipError_t begin(int n) {
+    if (!ctx->ring_timing) {
+      hipError_t e = hipEventRecord(ctx->ev0, ctx->stream);
+      if (e != hipSuccess) return e;
+    }
+    ev_start = ctx->evp[0];
+    ev_end = ctx->evp[1];
+    timed = !ctx->ring_timing || (ctx->ring_group && n > 1) || (ctx->ring_skip++ & 3) == 0;
+    if (ctx->ring_timing && timed) {
+      ev_start = ctx->ring[2 * ctx->ring_pos];
+      ev_end = ctx->ring[2 * ctx->ring_pos + 1];
+      ctx->ring_members[ctx->ring_pos] = n;
+      ctx->ring_has_red[ctx->ring_pos] = false;
+      if (ctx->ring_group && n > 1) {
+        ev_red = ctx->ring_red[ctx->ring_pos];
+        ctx->ring_has_red[ctx->ring_pos] = ev_red != nullptr;
+      }
+      ctx->ring_pos = (ctx->ring_pos + 1) % 64;
+      if (ctx->ring_n < 64) ++ctx->ring_n;
+    }
+    return timed ? hipEventRecord(ev_start, ctx->stream) : hipSuccess;
+  }
+  hipError_t after_kernel() { return timed ? hipEventRecord(ev_end, ctx->stream) : hipSuccess; }
+  hipError_t after_reduction() {
+    hipError_t e = ev_red ? hipEventRecord(ev_red, ctx->stream) : hipSuccess;
+    if (e == hipSuccess && !ctx->ring_timing) e = hipEventRecord(ctx->ev1, ctx->stream);
+    if (e == hipSuccess && !ctx->ring_timing) e = hipEventRecord(ctx->evp[2], ctx->stream);
+    return e;
+  }
+};
+}  // namespace
+
+// the kernel's arguments for a launch in `form` with geometry `g`; lift: the dictionary's slot table where form.lo
+static Gram3Args gram3_args(const kp_basis* basis, const kp_gram3_plan& plan, const Gram3Form& form, const Gram3Geometry& g, const kp_snapshots* const* ss, int n,
+                            double* part, const double* pre_buf, const uint32_t* lift) {
   const BasisDev& b = basis->dev;
   const kp_snapshots* s = ss[0];
-  if (n < 1 || n > KP_GRAM_GROUP_MAX) return ctx->fail(KP_ERR_ARG, "kp_fit_gram: bad group size");
-  for (int f = 0; f < n; ++f)
-    if (ss[f]->nzeta != b.nzeta || ss[f]->m != b.m || ss[f]->Ns != s->Ns) return ctx->fail(KP_ERR_ARG, "kp_fit_gram: snapshot/basis dimension mismatch");
-  const int W = b.W, N = b.N;
-  const int BM = b.m, NWT = (BM + 1) * (BM + 2) / 2;
-  kp_gram3_plan* planp = nullptr;
-  {
-    int rc = gram3_plan_for(ctx, basis, cover, &planp);
-    if (rc) return rc;
-  }
-  kp_gram3_plan& plan = *planp;
-  const int nfull4 = (b.nfull + 3) / 4 * 4;
-  const bool ext = gram3_ext(basis);
-  
-  int64_t ktiles = (s->Ns + KT3 - 1) / KT3;
-  int ncu, wg_per_cu;
-  const int64_t slots = gram3_slots(ctx, &ncu, &wg_per_cu);
-  // (per fit: the fits of a group launch share the chip)
-  int nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(ktiles, slots / plan.nsuper / n > 0 ? slots / plan.nsuper / n : 1));
-  int kps = (int)((ktiles + nsplit - 1) / nsplit);
-  if (kps < 1) kps = 1;
-  nsplit = (int)std::max<int64_t>(1, (ktiles + kps - 1) / kps);
-  size_t per_split = (size_t)plan.njobs * plan.nq * NWT * 64;
-  // the split partials (workspace 4), sized for the largest split count of this dictionary at once: a workspace that grows
-  // with the snapshot count would put a hipFree + hipMalloc of ~80 MB (17 ms, and a device synchronisation) into the first large fit of a running pipeline
-  // (... and for both plans of the dictionary, the cover plan built now if it has one: synchronous and pipelined fits of it
-  // may alternate, whichever comes first)
-  if (gram3_cover_mode() != 0) {
-    kp_gram3_plan* cov = nullptr;
-    int rc = gram3_cover_plan(ctx, basis, &cov);
-    if (rc) return rc;
-  }
-  size_t part_max = ((size_t)std::max<int64_t>((int64_t)n * nsplit, (int64_t)ncu * wg_per_cu / plan.nsuper) * per_split * 8 + 255) & ~(size_t)255;
-  for (const kp_gram3_plan* o : {(const kp_gram3_plan*)basis->plan3, (const kp_gram3_plan*)basis->plan3->cover})
-    if (o && o != &plan)
-      part_max = std::max(part_max, ((size_t)((int64_t)ncu * wg_per_cu / o->nsuper) * o->njobs * o->nq * NWT * 64 * 8 + 255) & ~(size_t)255);
-  double* part = (double*)ctx->workspace(4, part_max);
-  if (!part) return ctx->fail(KP_ERR_HIP, "kp_fit_gram: out of device memory");
-
-  // dim_red dictionaries: the econ lift once per snapshot into a row buffer (kp_gram3_prelift.hip), the Gram kernel loads tiles of it.
-  // Round 4's prelift kernel walked its 84 columns in ~40 us however few threads ran, so the in-kernel projection won below
-  // ~45 000 pairs; round 5's works tile by tile: at the arm data's 11 999 pairs 0.040 against 0.053 ms of kernels
-  // (tools/arm_shape_latency.py with KP_GRAM3_PRELIFT_MIN_NS=0).  Below a few thousand pairs the second launch is not worth it.
-  static const int64_t pre_min_ns = [] { const char* e = getenv("KP_GRAM3_PRELIFT_MIN_NS"); return e ? (int64_t)atoll(e) : (int64_t)6000; }();
-  bool pre = gram3_prelift(basis) && s->Ns >= pre_min_ns;
-  if (n > 1 && !gram3_inl_mono(basis, pre)) return ctx->fail(KP_ERR_ARG, "kp_fit_gram: these fits cannot share a launch");
-  const int pre_rl = 8 * plan.G4 + 12;
-  double* pre_buf = nullptr;
-  if (pre) {
-    // the row buffer is ~0.7 - 1 KB per snapshot (7 - 10 GB at 1e7 pairs), in one piece: when it is more than a quarter of the
-    // device's memory, or cannot be had (a busy device, several contexts of a kp_multi on one GPU), the fit runs with the
-    // in-kernel lift instead of failing - same Grams, no buffer
-    const size_t pre_bytes = (size_t)ktiles * KT3 * pre_rl * 8;
-    if (ctx->hbm_bytes > 0 && pre_bytes > (size_t)ctx->hbm_bytes / 4) pre = false;
-    if (pre) {
-      pre_buf = (double*)ctx->workspace(14, pre_bytes);
-      if (!pre_buf) {
-        (void)hipGetLastError();
-        pre = false;
-      }
-    }
-  }
-  if (pre && !ext && !basis->d_pcsT) {
-    if (hipMalloc(&basis->d_pcsT, (size_t)b.nfull * 32 * 8) != hipSuccess) return ctx->fail(KP_ERR_HIP, "kp_fit_gram: out of device memory");
-    KP_HIP(ctx, kp_gram3_pcs_transpose_launch(b.pcs, b.nfull, b.k_pcs, (double*)basis->d_pcsT, ctx->stream));
-  }
-  const size_t lds = (size_t)(LDS3_DOUBLES + (b.k_pcs > 0 && !pre ? 2 * nfull4 * 16 : 0) + (ext && !pre ? LDS3_GAUSS_DOUBLES : 0)) * sizeof(double);
-
+  const bool ext = form.ext;
   Gram3Args a;
   a.b = b;
   a.alpha = s->alpha;
@@ -1328,7 +1214,7 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   a.Ns = s->Ns;
   a.G4 = plan.G4;
   a.nsuper = plan.nsuper;
-  a.ktiles_per_split = kps;
+  a.ktiles_per_split = g.kps;
   a.D = ext ? basis->ext_Dp + 2 * basis->ext_df : basis->pow_depth;
   a.recipes = (const uint32_t*)(ext ? basis->d_recipes_ext : basis->d_recipes);
   a.Dp = ext ? basis->ext_Dp : basis->pow_depth;
@@ -1338,87 +1224,87 @@ static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapsho
   a.desc = plan.desc;
   a.part = part;
   a.njobs = plan.njobs;
-  a.pcs = b.k_pcs > 0 && !pre ? b.pcs : nullptr;
-  a.nfull4 = nfull4;
-  a.pre = pre_buf;
-  a.pre_rl = pre_rl;
-  a.nsplit_fit = nsplit;
+  a.pcs = form.kind == GRAM3_PCS ? b.pcs : nullptr;
+  a.nfull4 = (b.nfull + 3) / 4 * 4;
+  a.pre = form.kind == GRAM3_PRE ? pre_buf : nullptr;
+  a.pre_rl = form.pre_rl;
+  a.nsplit_fit = g.nsplit;
   for (int f = 0; f < n; ++f) a.grp[f] = Gram3Src{ss[f]->alpha, ss[f]->beta, ss[f]->u};
-  const bool mono = gram3_inl_mono(basis, pre);
-  // the in-kernel-lift monomial form: three table entries where no recipe reads a fourth
-  a.pow3 = mono && basis->pow_depth <= 3 && gram3_pow3_on();
-  // ... and, in the same form, the lift's jobs in the slots of the dictionary's table (LO) where it has one
-  if (mono && gram3_lift_order_on()) {
-    int rc = gram3_lift_table(ctx, basis, &a.lift);
+  a.pow3 = form.p3;      // (pow3 and eb: nothing reads them; they keep the kernel's argument block the size it has)
+  a.lift = form.lo ? lift : nullptr;
+  a.eb = form.eb;
+  return a;
+}
+
+// ss[0 .. n): the snapshot objects of n fits of one dictionary and ONE snapshot count (n > 1: kp_gram3_groupable); their [G | C]
+// pairs go to GC_dev + f 2 W^2.  The launch is dealt over the fits (gram3_geometry).  n = 1 is the launch of a single fit, bit for bit.
+static int gram3_launch_n(kp_ctx* ctx, const kp_basis* basis_c, const kp_snapshots* const* ss, int n, double* GC_dev, bool cover) {
+  kp_basis* basis = const_cast<kp_basis*>(basis_c);
+  const BasisDev& b = basis->dev;
+  const kp_snapshots* s = ss[0];
+  if (n < 1 || n > KP_GRAM_GROUP_MAX) return ctx->fail(KP_ERR_ARG, "kp_fit_gram: bad group size");
+  for (int f = 0; f < n; ++f)
+    if (ss[f]->nzeta != b.nzeta || ss[f]->m != b.m || ss[f]->Ns != s->Ns) return ctx->fail(KP_ERR_ARG, "kp_fit_gram: snapshot/basis dimension mismatch");
+  const int W = b.W, N = b.N, BM = b.m, NWT = (BM + 1) * (BM + 2) / 2;
+  const Gram3Switches sw = gram3_switches();
+  // 1. the plan this launch runs - and the dictionary's cover plan built now if it has one: workspace 4 is sized for both
+  kp_gram3_plan* planp = nullptr;
+  int rc = gram3_plan_for(ctx, basis, cover, &planp);
+  if (rc) return rc;
+  const kp_gram3_plan& plan = *planp;
+  if (gram3_cover_mode() != 0) {
+    kp_gram3_plan* cov = nullptr;
+    rc = gram3_cover_plan(ctx, basis, &cov);
     if (rc) return rc;
   }
-  // ... and, with the ordered lift, the tile's barrier in front of its last quad steps (EB) where the tile has the room.  Not for
-  // a plan with jobs of two A groups at NQ = 6, m = 3: those waves carry a second A fragment across the tile boundary, and two
-  // of their five tile loops then reload registers from scratch (the register table; one-A-group plans, fewer
-  // quads and fewer weights have none)
-  a.eb = mono && gram3_early_barrier_on() && gram3_tile_timing(plan.nq, a.lift != nullptr, true).bs >= 0 &&
-         (plan.two_group_jobs == 0 || plan.nq < 6 || BM < 3);
-  const int grid = plan.nsuper * nsplit * n;
-  // every event record is a barrier packet the command processor works through between two Gram kernels: the
-  // pipelined path (ring_timing) keeps two (kernel start / end)
-  if (!ctx->ring_timing) KP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  hipEvent_t ev_start = ctx->evp[0], ev_end = ctx->evp[1];
-  // deferred-solve pipeline: every event record is a barrier packet between two Gram kernels, so only every 4th launch
-  // is timed (the mean over the ring is what kp_synchronize reports)
-  // A group launch (ring_group: the Gram queue of kp_fit.hip, group size > 1) of several fits is always timed - one event pair
-  // per group is the packet rate of every 4th single launch - and so is its reduction (ring_red, timer 6).  A group of ONE
-  // keeps the every-4th rule and records no third event.
-  const bool timed = !ctx->ring_timing || (ctx->ring_group && n > 1) || (ctx->ring_skip++ & 3) == 0;
-  hipEvent_t ev_red = nullptr;
-  if (ctx->ring_timing && timed) {                // pipelined fits: a ring of event pairs, averaged at kp_synchronize
-    ev_start = ctx->ring[2 * ctx->ring_pos];
-    ev_end = ctx->ring[2 * ctx->ring_pos + 1];
-    ctx->ring_members[ctx->ring_pos] = n;
-    ctx->ring_has_red[ctx->ring_pos] = false;
-    if (ctx->ring_group && n > 1) {   // (a group of one records what a single launch recorded before: nothing behind its reduction)
-      ev_red = ctx->ring_red[ctx->ring_pos];
-      ctx->ring_has_red[ctx->ring_pos] = ev_red != nullptr;
-    }
-    ctx->ring_pos = (ctx->ring_pos + 1) % 64;
-    if (ctx->ring_n < 64) ++ctx->ring_n;
+  Gram3Facts f = gram3_facts(ctx, basis, plan, s->Ns, n);
+  const uint32_t* lift = nullptr;
+  if (gram3_mono(f, sw) && sw.lift_order) {
+    rc = gram3_lift_table(ctx, basis, &lift);
+    if (rc) return rc;
   }
-  if (timed) KP_HIP(ctx, hipEventRecord(ev_start, ctx->stream));
-  hipError_t e;
-  if (pre && ext)
-    KP_HIP(ctx, kp_gram3_prelift_ext_launch(BM, s->alpha, s->beta, s->u, s->Ns, ktiles * KT3, b.nzeta, basis->ext_Dp, basis->ext_df, basis->ext_ng, b.nfull, plan.G4,
-                                            (const uint32_t*)basis->d_recipes_ext, b.centres, pre_buf, pre_rl, ctx->stream));
+  f.lift_table = lift != nullptr;
+  // 2. geometry, 3. the split partials
+  const Gram3Geometry g = gram3_geometry(f);
+  double* part = (double*)ctx->workspace(4, g.ws4_bytes);
+  if (!part) return ctx->fail(KP_ERR_HIP, "kp_fit_gram: out of device memory");
+  // 4. form: asked once, the prelift buffer tried where one is wanted, asked again where there is none
+  Gram3Form form = gram3_form(f, sw, true);
+  if (form.refusal) return ctx->fail(KP_ERR_ARG, form.refusal);
+  double* pre_buf = form.want_buffer ? (double*)ctx->workspace(14, form.pre_bytes) : nullptr;
+  if (form.want_buffer && !pre_buf) {
+    (void)hipGetLastError();
+    form = gram3_form(f, sw, false);
+  }
+  const bool pre = form.kind == GRAM3_PRE;
+  if (pre && !form.ext && !basis->d_pcsT) {
+    if (hipMalloc(&basis->d_pcsT, (size_t)b.nfull * 32 * 8) != hipSuccess) return ctx->fail(KP_ERR_HIP, "kp_fit_gram: out of device memory");
+    KP_HIP(ctx, kp_gram3_pcs_transpose_launch(b.pcs, b.nfull, b.k_pcs, (double*)basis->d_pcsT, ctx->stream));
+  }
+  // 5. arguments, 6. prelift, 7. kernel, 8. reduction
+  const Gram3Args a = gram3_args(basis, plan, form, g, ss, n, part, pre_buf, lift);
+  Gram3Events ev{ctx};
+  KP_HIP(ctx, ev.begin(n));
+  if (pre && form.ext)
+    KP_HIP(ctx, kp_gram3_prelift_ext_launch(BM, s->alpha, s->beta, s->u, s->Ns, g.ktiles * KT3, b.nzeta, basis->ext_Dp, basis->ext_df, basis->ext_ng, b.nfull, plan.G4,
+                                            (const uint32_t*)basis->d_recipes_ext, b.centres, pre_buf, form.pre_rl, ctx->stream));
   else if (pre)
-    KP_HIP(ctx, kp_gram3_prelift_launch(BM, s->alpha, s->beta, s->u, s->Ns, ktiles * KT3, b.nzeta, basis->pow_depth, b.nfull, b.k_pcs, N, plan.G4,
-                                        (const uint32_t*)basis->d_recipes, (const double*)basis->d_pcsT, pre_buf, pre_rl, ctx->stream));
-  switch (plan.nq) {
-    case 1: e = launch3<1>(a, BM, grid, lds, ctx->stream); break;
-    case 2: e = launch3<2>(a, BM, grid, lds, ctx->stream); break;
-    case 3: e = launch3<3>(a, BM, grid, lds, ctx->stream); break;
-    case 4: e = launch3<4>(a, BM, grid, lds, ctx->stream); break;
-    case 5: e = launch3<5>(a, BM, grid, lds, ctx->stream); break;
-    default: e = launch3<6>(a, BM, grid, lds, ctx->stream); break;
-  }
-  KP_HIP(ctx, e);
-  if (timed) KP_HIP(ctx, hipEventRecord(ev_end, ctx->stream));
-  hipLaunchKernelGGL(kp_gram3_reduce_kernel, dim3(plan.njobs * plan.nq * NWT, n), dim3(nsplit >= 128 ? 1024 : nsplit >= 32 ? 512 : 256), 0, ctx->stream, part, nsplit, plan.njobs,
+    KP_HIP(ctx, kp_gram3_prelift_launch(BM, s->alpha, s->beta, s->u, s->Ns, g.ktiles * KT3, b.nzeta, basis->pow_depth, b.nfull, b.k_pcs, N, plan.G4,
+                                        (const uint32_t*)basis->d_recipes, (const double*)basis->d_pcsT, pre_buf, form.pre_rl, ctx->stream));
+  KP_HIP(ctx, gram3_dispatch(form, a, g.grid, gram3_lds_bytes(f, form), ctx->stream));
+  KP_HIP(ctx, ev.after_kernel());
+  hipLaunchKernelGGL(kp_gram3_reduce_kernel, dim3(plan.njobs * plan.nq * NWT, n), dim3(g.reduce_block), 0, ctx->stream, part, g.nsplit, plan.njobs,
                      plan.nq, NWT, BM, plan.desc, plan.G4, N, W, GC_dev, GC_dev + (size_t)W * W, plan.dst_off, plan.dst);
   KP_HIP(ctx, hipGetLastError());
-  if (ev_red) KP_HIP(ctx, hipEventRecord(ev_red, ctx->stream));
-  if (!ctx->ring_timing) {
-    KP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    KP_HIP(ctx, hipEventRecord(ctx->evp[2], ctx->stream));
-  }
+  KP_HIP(ctx, ev.after_reduction());
+  // 9. what ran
+  const Gram3Ran ran = gram3_ran(f, form);
   ctx->gram_flops_per_pair = (double)W * (W + 1) + 2.0 * W * W;
-  // executed on the matrix pipe per pair (timer 10), of the plan THIS launch ran: jobs (padding included) x quads x weights MFMAs per 4 snapshots, 512 flop
-  // each; dim_red: + the projection pcs' psi of every workgroup of a split (2 x nfull4 / 4 MFMAs per wave and tile)
-  ctx->timers[10] = (double)plan.njobs * plan.nq * NWT * 128.0 + (b.k_pcs > 0 && !pre ? (double)plan.nsuper * nfull4 * 128.0 : 0.0);
-  // table entries per raw value that the in-loop build of this launch's kernel writes (0: a form without that build)
-  ctx->timers[16] = !gram3_inl(basis, pre) ? 0.0 : a.pow3 ? 3.0 : 4.0;
-  // the lift order this launch ran: 1 the dictionary's slot table, 0 the order e = tid + 256 j (a form without the in-kernel monomial lift too)
-  ctx->timers[20] = a.lift ? 1.0 : 0.0;
-  // where this launch's tiles had their barrier: 1 in front of the last quad steps, 0 behind the last one
-  ctx->timers[26] = a.eb ? 1.0 : 0.0;
-  ctx->timers[15] = (double)plan.two_group_jobs;   // jobs of this launch's plan that span two A groups (0: a one-A-group plan)
+  ctx->timers[10] = ran.mfma_flop_per_pair;
+  ctx->timers[15] = ran.two_group_jobs;
+  ctx->timers[16] = ran.table_entries;
+  ctx->timers[20] = ran.lift_order;
+  ctx->timers[26] = ran.early_barrier;
   return KP_OK;
 }
 
@@ -1426,181 +1312,4 @@ int kp_gram3_launch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s, d
 
 int kp_gram3_launch_group(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* const* ss, int n, double* GC_dev) {
   return gram3_launch_n(ctx, basis, ss, n, GC_dev, true);
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------------
-// LINEAR models with dim_red (the first model of the reference's example_sysid.m: poly-3, econ lift [zeta; pcs' psi; 1]).
-// Their row [psi(x), u] is a column subset of the BILINEAR row psi (x) [1; u] of the same dictionary - the last dictionary
-// column is the constant, so u_i = psi_N u_i is column (i + 1) N + N - 1 of it - hence G and C of the linear fit are
-// sub-blocks of the bilinear Grams.  The only kernel that served these dictionaries was the general one (two-stage lift through
-// LDS, v_mfma_f64_16x16x4: 0.55 ms per 1e5 pairs at N = 34); the Kronecker kernel with the in-kernel projection forms the
-// bilinear Grams of the same dictionary in 0.21 ms, and a gather of (N + m)^2 entries makes the linear ones of them.
-// ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void kp_gram3_linear_gather_kernel(const double* __restrict__ GCb, int N, int m, int Wb, double* __restrict__ GC) {
-  const int W = N + m;
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= 2 * W * W) return;
-  const int which = e / (W * W), r = e - which * W * W, i = r % W, j = r / W;
-  const int bi = i < N ? i : (i - N + 1) * N + N - 1, bj = j < N ? j : (j - N + 1) * N + N - 1;
-  GC[e] = GCb[(size_t)which * Wb * Wb + (size_t)bj * Wb + bi];
-}
-
-static kp_basis* gram3_shadow(const kp_basis* basis_c) {
-  kp_basis* basis = const_cast<kp_basis*>(basis_c);
-  if (!basis->shadow_bil) {
-    kp_basis* sh = new kp_basis(*basis);               // shares every device array (never freed through the shadow)
-    sh->dev.model_type = KP_MODEL_BILINEAR;
-    sh->dev.W = sh->dev.N * (sh->dev.m + 1);
-    sh->plan = nullptr; sh->plan2 = nullptr; sh->plan3 = nullptr; sh->plan5 = nullptr; sh->shadow_bil = nullptr;
-    sh->d_pcsT = nullptr;                              // (its own transposed projection matrix, built on first use)
-    basis->shadow_bil = sh;
-  }
-  return basis->shadow_bil;
-}
-
-void kp_gram3_shadow_free(kp_basis* basis) {
-  if (!basis) return;
-  if (basis->shadow_bil) {
-    kp_gram3_plan_free(basis->shadow_bil->plan3);
-    if (basis->shadow_bil->d_pcsT) (void)hipFree(basis->shadow_bil->d_pcsT);
-    delete basis->shadow_bil;
-    basis->shadow_bil = nullptr;
-  }
-  if (basis->shadow_full) {
-    kp_gram_plan_free(basis->shadow_full->plan);
-    kp_gram2_plan_free(basis->shadow_full->plan2);
-    kp_gram5_plan_free(basis->shadow_full->plan5);
-    delete basis->shadow_full;
-    basis->shadow_full = nullptr;
-  }
-}
-
-bool kp_gram3_linear_applicable(const kp_basis* basis) {
-  const BasisDev& b = basis->dev;
-  if (b.model_type != KP_MODEL_LINEAR || b.k_pcs <= 0 || b.m < 1 || getenv("KP_NO_GRAM3_LINEAR")) return false;
-  return kp_gram3_applicable(gram3_shadow(basis));
-}
-
-int kp_gram3_linear_launch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s, double* GC_dev) {
-  kp_basis* sh = gram3_shadow(basis);
-  const int N = basis->dev.N, m = basis->dev.m, W = basis->dev.W, Wb = sh->dev.W;
-  double* tmp = (double*)ctx->workspace(10, (size_t)2 * Wb * Wb * 8);
-  if (!tmp) return ctx->fail(KP_ERR_HIP, "kp_fit_gram: out of device memory");
-  int rc = kp_gram3_launch(ctx, sh, s, tmp);
-  if (rc) return rc;
-  hipLaunchKernelGGL(kp_gram3_linear_gather_kernel, dim3((2 * W * W + 255) / 256), dim3(256), 0, ctx->stream, tmp, N, m, Wb, GC_dev);
-  KP_HIP(ctx, hipGetLastError());
-  ctx->gram_flops_per_pair = (double)W * (W + 1) + 2.0 * W * W;
-  // timer 10 (flop EXECUTED on the matrix pipe per pair) stays what the inner launch set: the work added here - the gather, the
-  // congruence products 2 (Wf^2 W + Wf W^2) flop - is per FIT and runs on the vector pipe, so it is in the kernel time of the
-  // bench's roofline block but, rightly, not in its matrix-pipe flop
-  return KP_OK;
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------------
-// dim_red dictionaries of LINEAR and NONLINEAR models (the first and third model of the reference's example_sysid.m).  The
-// econ lift [v; pcs' psi_full(v); 1] (Ksysid.m:1594-1618) is a LINEAR map of the full lift - the variables are the first
-// columns of the full dictionary, the constant its last -  psi_econ = T' psi_full,  T = [E_vars | pcs | e_const]  (and the
-// identity on the input columns of a linear row), so
-//     G_econ = T' (Psi_x' Psi_x) T,      C_econ = T' (Psi_x' Psi_y) T :
-// the full dictionary's Grams by the monomial kernels (kp_gram5 / kp_gram2: 0.115 ms linear, 0.34 ms nonlinear poly-3 per 1e5
-// pairs) and two small congruence products, instead of the general kernel's per-pair projection through LDS (0.55 ms and
-// 4.2 ms).  Bilinear dim_red dictionaries keep the Kronecker kernel with the in-kernel projection (0.21 ms against 0.40 ms).
-// ---------------------------------------------------------------------------------------------------------------------
-struct CongT { int nvars, k, nfull, N, W, Wf; const double* pcs; };
-// entry of T: row c of the full row layout (dictionary columns, then the inputs of a linear row), econ column j
-__device__ __forceinline__ int cong_unit(const CongT& t, int j) {        // >= 0: T(:, j) = e_idx; -1: a pcs column
-  if (j < t.nvars) return j;
-  if (j < t.nvars + t.k) return -1;
-  if (j == t.N - 1) return t.nfull - 1;
-  return t.nfull + (j - t.N);                                            // input columns of a linear row
-}
-// R (Wf x W) = M (Wf x Wf) T, for M = G_full and C_full (blockIdx.y)
-__global__ __launch_bounds__(256) void kp_cong_right_kernel(const double* __restrict__ GCf, CongT t, double* __restrict__ R) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= t.Wf * t.W) return;
-  const int i = e % t.Wf, j = e / t.Wf;
-  const double* M = GCf + (size_t)blockIdx.y * t.Wf * t.Wf;
-  const int u = cong_unit(t, j);
-  double v;
-  if (u >= 0) v = M[i + (size_t)u * t.Wf];
-  else {
-    const double* pc = t.pcs + (size_t)(j - t.nvars) * t.nfull;
-    double s0 = 0.0, s1 = 0.0;
-    int c = 0;
-    for (; c + 1 < t.nfull; c += 2) { s0 += M[i + (size_t)c * t.Wf] * pc[c]; s1 += M[i + (size_t)(c + 1) * t.Wf] * pc[c + 1]; }
-    if (c < t.nfull) s0 += M[i + (size_t)c * t.Wf] * pc[c];
-    v = s0 + s1;
-  }
-  R[(size_t)blockIdx.y * t.Wf * t.W + e] = v;
-}
-// out (W x W) = T' R
-__global__ __launch_bounds__(256) void kp_cong_left_kernel(const double* __restrict__ R, CongT t, double* __restrict__ GC) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= t.W * t.W) return;
-  const int i = e % t.W, j = e / t.W;
-  const bool sym = blockIdx.y == 0;                    // G: one triangle is computed and mirrored (exactly symmetric, like the kernels' own G)
-  if (sym && i > j) return;
-  const double* Rj = R + (size_t)blockIdx.y * t.Wf * t.W + (size_t)j * t.Wf;
-  const int u = cong_unit(t, i);
-  double v;
-  if (u >= 0) v = Rj[u];
-  else {
-    const double* pc = t.pcs + (size_t)(i - t.nvars) * t.nfull;
-    double s0 = 0.0, s1 = 0.0;
-    int c = 0;
-    for (; c + 1 < t.nfull; c += 2) { s0 += pc[c] * Rj[c]; s1 += pc[c + 1] * Rj[c + 1]; }
-    if (c < t.nfull) s0 += pc[c] * Rj[c];
-    v = s0 + s1;
-  }
-  GC[(size_t)blockIdx.y * t.W * t.W + e] = v;
-  if (sym && i < j) GC[(size_t)j + (size_t)i * t.W] = v;
-}
-
-static kp_basis* gram_shadow_full(const kp_basis* basis_c) {
-  kp_basis* basis = const_cast<kp_basis*>(basis_c);
-  if (!basis->shadow_full) {
-    kp_basis* sh = new kp_basis(*basis);               // shares every device array (never freed through the shadow)
-    sh->dev.k_pcs = 0;
-    sh->dev.pcs = nullptr;
-    sh->d_pcs = nullptr;
-    sh->dev.N = sh->dev.nfull;
-    sh->dev.W = sh->dev.model_type == KP_MODEL_LINEAR ? sh->dev.nfull + sh->dev.m : sh->dev.nfull;
-    sh->plan = nullptr; sh->plan2 = nullptr; sh->plan3 = nullptr; sh->plan5 = nullptr; sh->shadow_bil = nullptr; sh->shadow_full = nullptr;
-    sh->d_pcsT = nullptr;
-    basis->shadow_full = sh;
-  }
-  return basis->shadow_full;
-}
-
-bool kp_gram_congruence_applicable(const kp_basis* basis) {
-  const BasisDev& b = basis->dev;
-  if ((b.model_type != KP_MODEL_LINEAR && b.model_type != KP_MODEL_NONLINEAR) || b.k_pcs <= 0 || b.N != b.nvars + b.k_pcs + 1 ||
-      getenv("KP_NO_GRAM_CONGRUENCE"))
-    return false;
-  const kp_basis* sh = gram_shadow_full(basis);
-  return kp_gram5_applicable(sh) || kp_gram2_applicable(sh);
-}
-
-int kp_gram_congruence_launch(kp_ctx* ctx, const kp_basis* basis, const kp_snapshots* s, double* GC_dev) {
-  kp_basis* sh = gram_shadow_full(basis);
-  const BasisDev& b = basis->dev;
-  const int W = b.W, Wf = sh->dev.W;
-  double* GCf = (double*)ctx->workspace(10, (size_t)2 * Wf * Wf * 8);
-  double* R = (double*)ctx->workspace(11, (size_t)2 * Wf * W * 8);
-  if (!GCf || !R) return ctx->fail(KP_ERR_HIP, "kp_fit_gram: out of device memory");
-  hipStream_t rs = ctx->stream;                       // kp_gram5 / kp_gram2 reduce on the Gram stream
-  int rc = kp_gram5_applicable(sh) ? kp_gram5_launch(ctx, sh, s, GCf) : kp_gram2_launch(ctx, sh, s, GCf);
-  if (rc) return rc;
-  CongT t{b.nvars, b.k_pcs, b.nfull, b.N, W, Wf, b.pcs};
-  hipLaunchKernelGGL(kp_cong_right_kernel, dim3((Wf * W + 255) / 256, 2), dim3(256), 0, rs, GCf, t, R);
-  hipLaunchKernelGGL(kp_cong_left_kernel, dim3((W * W + 255) / 256, 2), dim3(256), 0, rs, R, t, GC_dev);
-  KP_HIP(ctx, hipGetLastError());
-  ctx->gram_flops_per_pair = (double)W * (W + 1) + 2.0 * W * W;
-  // timer 10 (flop EXECUTED on the matrix pipe per pair) stays what the inner launch set: the work added here - the gather, the
-  // congruence products 2 (Wf^2 W + Wf W^2) flop - is per FIT and runs on the vector pipe, so it is in the kernel time of the
-  // bench's roofline block but, rightly, not in its matrix-pipe flop
-  return KP_OK;
 }

@@ -34,12 +34,13 @@ struct Gram3Args {
   // has nsplit_fit = its split count and grp[0] = (alpha, beta, u)
   int nsplit_fit = 1 << 30;
   Gram3Src grp[KP_GRAM_GROUP_MAX] = {};
-  // launcher only: the in-kernel-lift monomial form of a dictionary without fourth powers runs its three-entry table (P3)
+  // launcher only (pow3 and eb: the kernel reads neither; they stay so that the argument block keeps its size and `lift` its
+  // offset): the in-kernel-lift monomial form of a dictionary without fourth powers runs its three-entry table (P3)
   bool pow3 = false;
   // the same form: its lift slot table (kp_gram3_lift.h: GRAM3_LIFT_SLOTS words) where the launch runs the ordered lift (LO),
   // nullptr where it runs the order e = tid + 256 j
   const uint32_t* lift = nullptr;
-  // the same form: the tile's barrier sits in front of its last quad steps (EB; kp_gram3.hip: gram3_tile_timing)
+  // the same form: the tile's barrier sits in front of its last quad steps (EB; kp_gram3_launch.h: gram3_tile_timing)
   bool eb = false;
 };
 

@@ -179,8 +179,8 @@ struct kp_basis {
   kp_gram2_plan* plan2 = nullptr;  // plan of the 4x4x4-MFMA Gram kernel (monomial dictionaries)
   kp_gram3_plan* plan3 = nullptr;  // plan of the Kronecker (bilinear) Gram kernel
   kp_gram5_plan* plan5 = nullptr;  // plan of the dense 4x4x4 Gram kernel (linear / nonlinear monomial dictionaries)
-  kp_basis* shadow_bil = nullptr;  // linear dim_red dictionaries: the same dictionary as a BILINEAR one (shares every device array; kp_gram3.hip)
-  kp_basis* shadow_full = nullptr; // linear / nonlinear dim_red dictionaries: the same dictionary WITHOUT the projection (kp_gram3.hip)
+  kp_basis* shadow_bil = nullptr;  // linear dim_red dictionaries: the same dictionary as a BILINEAR one (shares every device array; kp_gram_shadow.hip)
+  kp_basis* shadow_full = nullptr; // linear / nonlinear dim_red dictionaries: the same dictionary WITHOUT the projection (kp_gram_shadow.hip)
   std::vector<uint32_t> h_recipes; // host copy of the recipes (valid if fast)
   // extended recipes of the Kronecker Gram kernel (kp_gram3): besides powers, the per-variable table may hold the
   // harmonics cos / sin(2 pi j x) of fourier blocks (Ksysid.m:694-731) and, behind the per-variable entries, one entry per
